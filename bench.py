@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Benchmark: env-steps/s of the batched Drone2dEnv step at 65 536 envs per MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]     (N > 1: starts its N ranks itself)
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
+                                                            (N > 1: starts its N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -21,8 +22,12 @@ collective in the step; the episode statistics are all-reduced once per timed in
 
 Prints ONE JSON line (rank 0).  ``roofline.achieved`` = 650 algorithmic bytes per env-step x envs
 per launch / mean step time on the device (HIP events on the launch stream around the timed
-steps: one pair around the eager loop, one per graph replay with --graph); ``cpu_baseline`` = the C
-oracle (a scalar port of the same algorithm) timed on this host's cores on a bounded sample.
+steps: one pair around the eager loop, one per graph replay with --graph).  A plain run sets up,
+warms up, times the steps and prints the line; ``--full`` adds ``cpu_baseline`` = the C oracle (a
+scalar port of the same algorithm) timed on this host's cores on a bounded sample.
+``--dump-outputs DIR`` writes the tensors the last timed step returned as ``DIR/<name>.npy``
+(float32; ranks > 0 of a multi-GPU run as ``<name>.rank<r>.npy``): envs, seeds and the action bank
+are fixed, so two builds run with the same arguments can be compared output for output.
 """
 from __future__ import annotations
 
@@ -62,8 +67,13 @@ def parse():
     p.add_argument("--scenario", default=SCENARIO,
                    help="test scenario name, NAME_free (no obstacles: configs[1]), 'mixed' (configs[4]) or "
                         "'curriculum' (the fresh training curriculum: a new device-generated scenario per episode)")
-    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget (s)")
-    p.add_argument("--no-cpu-baseline", action="store_true")
+    p.add_argument("--full", action="store_true",
+                   help="also run what the headline figure does not need: the CPU baseline (cpu_baseline in the line)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="after the timed steps, write what the last timed step returned (obs, reward, terminated, "
+                        "truncated, terminal_obs, info with --info) as DIR/<name>.npy (float32)")
+    p.add_argument("--cpu-seconds", type=float, default=12.0, help="CPU baseline sample budget (s), with --full")
+    p.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     p.add_argument("--clock-warmup-ms", type=float, default=100.0,
                    help="device clock warm-up before the warmup steps: the step kernels on a separate "
                         "throwaway batch (the measured envs are untouched); 0 disables")
@@ -297,6 +307,20 @@ def cpu_baseline(args, kwargs):
                       f"{dt:.1f} s; single core: {steps1} steps, {dt1:.1f} s"}
 
 
+def dump_outputs(path: str, out, rank: int) -> None:
+    """``--dump-outputs``: the tensors the last timed step returned (``venv.step``'s tuple and the
+    terminal observations, rows of envs that did not finish in that step zeroed: they hold an earlier
+    episode's), whole, as float32 ``<name>.npy`` (65 536 envs: 15 MB, 18 MB with info)."""
+    os.makedirs(path, exist_ok=True)
+    sfx = f".rank{rank}" if rank else ""
+    obs, rew, term, trunc, info, tobs = out
+    tobs = torch.where((term | trunc).unsqueeze(1), tobs, torch.zeros_like(tobs))
+    for name, t in zip(("obs", "reward", "terminated", "truncated", "info", "terminal_obs"),
+                       (obs, rew, term, trunc, info, tobs)):
+        if t is not None:
+            np.save(os.path.join(path, f"{name}{sfx}.npy"), t.to(torch.float32).cpu().numpy())
+
+
 def main():
     args = parse()
     if args.gpus < 1:
@@ -337,12 +361,15 @@ def main():
     reps, rem = divmod(args.steps, glen)
     graph = tail = None
     hipgraph = args.graph and not args.eager
+    out = None  # what the last timed step returned (--dump-outputs)
     if hipgraph:
         def capture(n_steps):
+            nonlocal out
             g = torch.cuda.CUDAGraph()
             with torch.cuda.graph(g):
                 for k in range(n_steps):
-                    venv.step(bank[k % ACTION_BANK])
+                    out = venv.step(bank[k % ACTION_BANK])
+            out = (*out, venv.terminal_obs)
             return g
         if reps:
             graph = capture(glen)
@@ -396,12 +423,16 @@ def main():
     else:
         starts[0].record(stream)
         for k in range(args.steps):
-            venv.step(bank[k % ACTION_BANK])
+            out = venv.step(bank[k % ACTION_BANK])
         ends[0].record(stream)
     n_timed = args.steps
     barrier_sync(world)
     wall = time.perf_counter() - t0
     clk["after_timed"] = gpu_clock(card)
+    if args.dump_outputs:
+        if not hipgraph:
+            out = (*out, venv.terminal_obs)
+        dump_outputs(args.dump_outputs, out, rank)
 
     # episode statistics of the interval: the one RCCL all-reduce (timed separately)
     stats = venv.episode_stats(clear=True)
@@ -516,7 +547,7 @@ def main():
                                           f"stage from the device step clock), {n} envs per GPU, U(-1,1) f32 "
                                           f"actions, in-kernel auto-reset")
             line["kernel_note"] = "per step: step kernel + scenario generator (K5) + queue clear + fill/16"
-        elif not args.no_cpu_baseline and world == 1:
+        elif args.full and not args.no_cpu_baseline and world == 1:
             line["cpu_baseline"] = cpu_baseline(args, kwargs)
         print(json.dumps(line), flush=True)
     venv.close()

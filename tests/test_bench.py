@@ -74,6 +74,54 @@ def test_bench_gpus_flag_launches_its_ranks():
         assert two["episodes"][k] == one["episodes"][k], k
 
 
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_reproducible_outputs(tmp_path):
+    """A plain run (no --full) has no CPU baseline in its line, times exactly --steps steps, and with
+    --dump-outputs writes the last timed step's outputs as float32 .npy, identical from run to run."""
+    import numpy as np
+
+    env = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
+    dumps = []
+    for tag in ("a", "b"):
+        d = tmp_path / tag
+        line = _run([sys.executable, "bench.py", "--gpus", "1", "--envs", "4160", "--steps", "24", "--warmup", "40",
+                     "--info", "--dump-outputs", str(d)], env)
+        assert "cpu_baseline" not in line and line["steps"] == 24 and line["ms_per_step"] > 0
+        dumps.append({f: np.load(d / f) for f in sorted(os.listdir(d))})
+    a, b = dumps
+    assert sorted(a) == ["info.npy", "obs.npy", "reward.npy", "terminal_obs.npy", "terminated.npy", "truncated.npy"]
+    assert a["obs.npy"].shape == a["terminal_obs.npy"].shape == (4160, 27) and a["info.npy"].shape == (4160, 12)
+    for f in a:
+        assert a[f].dtype == np.float32 and a[f].shape[0] == 4160
+        assert np.array_equal(a[f], b[f], equal_nan=True), f
+    done = (a["terminated.npy"] + a["truncated.npy"]) > 0
+    assert done.any() and not done.all()  # 64 steps of random actions: some envs end in the last step
+    assert np.abs(a["obs.npy"]).max() > 0 and not a["terminal_obs.npy"][~done].any()
+    assert np.abs(a["terminal_obs.npy"][done]).max() > 0
+
+
+def test_dump_outputs_writes_float32_npy(tmp_path):
+    """dump_outputs: step's tuple + terminal obs as float32 <name>.npy; no info file without info
+    rows; terminal-obs rows of envs that did not finish are zero; ranks > 0 get a .rank<r> suffix."""
+    import numpy as np
+    import torch
+
+    sys.path.insert(0, REPO)
+    import bench
+
+    obs, tobs = torch.arange(6.0).reshape(3, 2), torch.full((3, 2), float("nan"))
+    tobs[1] = 7.0
+    term, trunc = torch.tensor([False, True, False]), torch.tensor([False, False, False])
+    bench.dump_outputs(str(tmp_path / "d"), (obs, torch.ones(3), term, trunc, None, tobs), 0)
+    got = {f: np.load(tmp_path / "d" / f) for f in os.listdir(tmp_path / "d")}
+    assert sorted(got) == ["obs.npy", "reward.npy", "terminal_obs.npy", "terminated.npy", "truncated.npy"]
+    assert all(v.dtype == np.float32 for v in got.values())
+    assert got["terminated.npy"].tolist() == [0.0, 1.0, 0.0]
+    assert got["terminal_obs.npy"].tolist() == [[0.0, 0.0], [7.0, 7.0], [0.0, 0.0]]
+    bench.dump_outputs(str(tmp_path / "d"), (obs, torch.ones(3), term, trunc, torch.zeros(3, 12), tobs), 1)
+    assert os.path.exists(tmp_path / "d" / "info.rank1.npy") and not os.path.exists(tmp_path / "d" / "info.npy")
+
+
 def test_bench_refuses_world_mismatch():
     """Under a launcher whose world differs from --gpus the bench exits non-zero before any GPU work."""
     env = dict(os.environ, WORLD_SIZE="1", RANK="0", LOCAL_RANK="0")

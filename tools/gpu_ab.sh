@@ -10,7 +10,7 @@ mkdir -p $O
 export TMPDIR=/tmp
 R=$(pwd)
 fail() { echo "STOP at $1 (rc $2)"; exit $2; }
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $O/bench_k20_first.log 2>&1 || fail bench_k20_first $?
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 > $O/bench_k20_first.log 2>&1 || fail bench_k20_first $?
 tail -1 $O/bench_k20_first.log
 if [ "${NOTEST:-0}" != 1 ]; then
   timeout -k 10 900 python -u -m pytest tests -m gpu -q --timeout 200 --timeout-method thread > $O/pytest_gpu.log 2>&1
@@ -26,9 +26,9 @@ print(d["scenario"], {k: round(v["ms_per_step_min"] * 1e3, 2) for k, v in d["var
 PY
   done
 fi
-timeout -k 10 200 python bench.py > $O/bench.log 2>&1 || fail bench $?
+timeout -k 10 200 python bench.py --full > $O/bench.log 2>&1 || fail bench $?
 tail -1 $O/bench.log | cut -c1-400
-timeout -k 10 200 python bench.py --steps 20 --warmup 5 > $O/bench_k20.log 2>&1 || fail bench_k20 $?
+timeout -k 10 200 python bench.py --full --steps 20 --warmup 5 > $O/bench_k20.log 2>&1 || fail bench_k20 $?
 if [ "${NOPROF:-0}" != 1 ]; then
   (cd /tmp && timeout -k 10 300 rocprofv3 --kernel-trace --stats -T --output-format csv -d $R/$O/kt -o kt -- python3 $R/bench.py --no-cpu-baseline > $R/$O/kt.log 2>&1) || fail rocprof $?
   find $O/kt -name '*kernel_stats.csv' -exec head -5 {} \;

@@ -23,8 +23,8 @@ run() {  # run <name> <timeout-s> <cmd...>: allow 0/1 (test failures), stop on a
 }
 run pytest_gpu 900 python -u -m pytest tests -m gpu -v --timeout 200 --timeout-method thread
 run smoke 300 python -c "import __graft_entry__ as g; g.smoke()"
-run bench_k20 300 python bench.py --steps 20 --warmup 5
-run bench 400 python bench.py
+run bench_k20 300 python bench.py --full --steps 20 --warmup 5
+run bench 400 python bench.py --full
 run configs 900 bash tools/configs.sh "$TAG"
 run profile 1100 bash tools/profile.sh "$TAG"
 run fresh 600 bash tools/gpu_fresh.sh "$TAG" drone-2d-custom-gym-env-for-reinforcement-learning_amd/_lib/libdrone2d_hip.so
