@@ -1,7 +1,7 @@
-// d2d_hip.hip -- kernels + C ABI of libdrone2d_hip.so (see include/drone2d.h).
-//
-// Kernels: see d2d_kernels.h (K1 cooperative step, K2 masked reset, K3 episode statistics, K4 reset
-// observation cache fill).
+// d2d_hip.hip -- C ABI of libdrone2d_hip.so (see include/drone2d.h): the handle, its device buffers,
+// and the launches of the kernels in d2d_kernels.h (K1 cooperative step, K2 masked reset, K3 episode
+// statistics, K4 reset observation cache fill, K5 fresh curriculum).  The slot layout's host code is
+// d2d_layout.h.
 #include <hip/hip_runtime.h>
 
 #include <algorithm>
@@ -9,15 +9,15 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <new>
 #include <string>
+#include <utility>
 #include <vector>
 
 #include "d2d_kernels.h"
 
 using namespace d2dk;
-
-
 
 namespace {
 thread_local std::string g_err;
@@ -30,89 +30,129 @@ int hip_fail(hipError_t e, const char* what) {
     return fail(D2D_E_HIP, std::string(what) + ": " + hipGetErrorString(e));
 }
 
+// Owned device memory: freed when the owner goes out of scope or is assigned over.
+struct HipFree {
+    void operator()(void* p) const { (void)hipFree(p); }
+};
+template <class T>
+using DevBuf = std::unique_ptr<T, HipFree>;
+// `count` elements of device memory set to the byte `fill`, the first n_src of them copied from host `src`
+template <class T>
+hipError_t dev_new(DevBuf<T>& out, size_t count, int fill = 0, const T* src = nullptr, size_t n_src = 0) {
+    void* p = nullptr;
+    hipError_t e = hipMalloc(&p, sizeof(T) * count);
+    if (e != hipSuccess) return e;
+    out.reset(static_cast<T*>(p));
+    if (n_src < count) e = hipMemset(p, fill, sizeof(T) * count);
+    if (e == hipSuccess && n_src) e = hipMemcpy(p, src, sizeof(T) * n_src, hipMemcpyHostToDevice);
+    return e;
+}
+
+// Internal arrays of one slot layout.
+struct Layout {
+    int ns = 0;  // state slots (columns of the [F][ns] arrays): n, or the grouped layout's 64 per group
+    DevBuf<double> st;
+    DevBuf<int32_t> ist;
+    DevBuf<double> acc;
+    // auto-reset observation cache (d2d_kernels.h, "Auto-reset observation cache")
+    DevBuf<float> rc_obs;    // [RC_SLOTS][ns][27]
+    DevBuf<int32_t> rc_rfl;  // [RC_SLOTS][ns]
+    DevBuf<int32_t> rc_tag;  // [RC_SLOTS][ns]
+    // scenario-grouped slot layout (StepArgs::lane_env); null: slot == env
+    DevBuf<int32_t> lane_env;  // [ns] slot -> env (-1: padding)
+    DevBuf<int32_t> wg_scn;    // [ns / EPB] scenario of each slot group
+    DevBuf<int32_t> env_slot;  // [n] env -> slot
+    bool grouped() const { return lane_env != nullptr; }
+    int n_groups() const { return grouped() ? ns / EPB : 0; }
+};
+// The scenario table and what is derived from it.
+struct ScnTables {
+    int n_scn = 0;              // entries (pool mode: both halves; fresh mode: 2 per env)
+    bool rm = false;            // the table's layout: ScnR where K1 reads it from global memory (place)
+    DevBuf<unsigned char> scn;  // ABI scenarios + derived fields, ScnF or ScnR
+    DevBuf<d2d::BrTab> brt;     // golden-march tables of the scenarios (d2d_brtab_kernel); fresh mode: none
+    DevBuf<d2d_scn> abi;        // ABI records of the table (pool and fresh modes: readback)
+};
+// Fresh curriculum: per scenario slot, the episode it was generated for, and K5's queue.
+struct FreshSlots {
+    DevBuf<int32_t> scn_tag;  // [2 n] episode key of each slot
+    DevBuf<int64_t> gclk;     // [2 n] clock at generation
+    DevBuf<int32_t> queue;    // [ring + FR_WORDS] K5's ring of slots to generate + its words
+    size_t ring = 0;          // ring size: the power of two >= 2 n
+    uint32_t* words() const { return reinterpret_cast<uint32_t*>(queue.get() + ring); }
+};
 }  // namespace
 
 struct d2d_handle {
     d2d_cfg cfg;
     int n = 0;
-    int ns = 0;   // state slots (columns of the internal [F][ns] arrays): n, or the grouped layout's
     int device = 0;
-    int n_scn = 0;
-    double* st = nullptr;
-    int32_t* ist = nullptr;
-    double* acc = nullptr;
-    void* scn = nullptr;        // device table: ABI scenarios + derived fields, ScnF or ScnR (rm)
-    bool rm = false;            // the table's layout: ScnR where K1 reads it from global memory
-    d2d::BrTab* brt = nullptr;  // golden-march tables of the scenarios (d2d_brtab_kernel)
-    int32_t* env_scn = nullptr;
+    int n_cu = 0;  // compute units of the device
+    Layout lay;
+    ScnTables tab;
+    FreshSlots fresh;
+    DevBuf<int32_t> env_scn;
     // pool mode: the scenario table has two halves of pool_n entries; resets draw from the half at
     // pool_base (host copy; the kernels read *pool_dev), d2d_refresh_pool fills and switches halves
     int pool_base = 0, pool_n = 0;
-    int32_t* pool_dev = nullptr;
-    int32_t* fill_ctl = nullptr;  // [2] K4's tick and finished-workgroup count
+    int pool_valid = 0;  // bit h = half h holds uploaded scenarios
+    DevBuf<int32_t> pool_dev;
+    DevBuf<int32_t> fill_ctl;  // [2] K4's tick and finished-workgroup count
+    DevBuf<int64_t> clock;     // [1] the step clock (K1 advances it)
     uint64_t seed = 0;
     bool reset_done = false;
-    uint64_t* stamps = nullptr;  // diagnostic builds (D2D_STAMPS) only
-    // auto-reset observation cache (d2d_kernels.h, "Auto-reset observation cache")
-    float* rc_obs = nullptr;     // [n][27]
-    int32_t* rc_rfl = nullptr;   // [n]
-    int32_t* rc_tag = nullptr;   // [n]
-    bool rc_dirty = true;        // scenarios changed since the cache was last dropped
-    // scenario-grouped slot layout (StepArgs::lane_env), built by d2d_set_scenarios
-    int32_t* lane_env = nullptr;  // [ns] slot -> env (-1: padding)
-    int32_t* wg_scn = nullptr;    // [ns / EPB] scenario of each slot group
-    int32_t* env_slot = nullptr;  // [n] env -> slot
-    int n_groups = 0;
+    uint64_t* stamps = nullptr;  // diagnostic builds (D2D_STAMPS) only; the caller's buffer
+    bool rc_dirty = true;        // scenarios changed since the reset cache was last dropped
     uint64_t n_steps = 0;        // d2d_step calls (fill cadence)
-    // pool / fresh curriculum
-    d2d_scn* abi = nullptr;      // [n_scn] ABI records of the table (pool and fresh modes: readback)
-    int pool_valid = 0;          // pool mode: bit h = half h holds uploaded scenarios
     d2d_curriculum cur{};        // fresh mode: generator parameters
-    int32_t* scn_tag = nullptr;  // fresh mode: [2 n] episode key of each slot
-    int64_t* gclk = nullptr;     // fresh mode: [2 n] clock at generation
-    int32_t* fresh_q = nullptr;  // fresh mode: [fresh_ring + FR_WORDS] K5's ring of slots to generate + its words
-    size_t fresh_ring = 0;       // ring size: the power of two >= 2 n
-    int64_t* clock = nullptr;    // [1] the step clock (K1 advances it)
     uint64_t fresh_seed = 0;
     bool fresh_seeded = false;
-    int32_t generation = 0;      // bumped whenever captured graphs' pointers go stale
-    int n_cu = 0;                      // compute units of the device
-    std::vector<double> scn_cost;      // relative step cost per scenario (d2d_set_scenario_costs)
+    int32_t generation = 0;        // bumped whenever captured graphs' pointers go stale
+    std::vector<double> scn_cost;  // relative step cost per scenario (d2d_set_scenario_costs)
+    // buffers were replaced: captured graphs point at the old ones, cached reset observations belong to them
+    void stale() {
+        generation += 1;
+        rc_dirty = true;
+    }
 };
 
 namespace {
 
+bool fresh_mode(const d2d_t* h) { return h->cfg.scn_pool == 2; }
+
+// the single place that flattens the handle into the kernels' arguments
 StepArgs make_args(const d2d_t* h) {
+    const Layout& L = h->lay;
     StepArgs a{};
     a.n = h->n;
-    a.ns = h->ns;
-    a.n_scn = h->n_scn;
-    a.st = h->st;
-    a.ist = h->ist;
-    a.acc = h->acc;
-    a.scn = h->scn;
-    a.brt = h->brt;  // (null in fresh curriculum mode: docs/DESIGN_HISTORY.md "Round 4")
-    a.env_scn = h->env_scn;
-    a.pool_base = h->pool_dev;
+    a.ns = L.ns;
+    a.n_scn = h->tab.n_scn;
+    a.st = L.st.get();
+    a.ist = L.ist.get();
+    a.acc = L.acc.get();
+    a.scn = h->tab.scn.get();
+    a.brt = h->tab.brt.get();  // (null in fresh curriculum mode: docs/DESIGN_HISTORY.md "Round 4")
+    a.env_scn = h->env_scn.get();
+    a.pool_base = h->pool_dev.get();
     a.pool_n = h->pool_n;
-    a.fill_ctl = h->fill_ctl;
+    a.fill_ctl = h->fill_ctl.get();
     a.fill_every = FILL_EVERY;
     a.fill_force = 0;
     a.cfg = h->cfg;
     a.damping_dt = std::pow(h->cfg.damping, 1.0 / 60.0);
     a.seed = h->seed;
     a.stamps = h->stamps;
-    a.rc_obs = h->rc_obs;
-    a.rc_rfl = h->rc_rfl;
-    a.rc_tag = h->rc_tag;
-    a.lane_env = h->lane_env;
-    a.wg_scn = h->wg_scn;
-    a.scn_tag = h->scn_tag;
-    a.clock = h->clock;
-    if (h->cfg.scn_pool == 2 && h->fresh_q) {
-        a.fq = h->fresh_q;
-        a.fqc = reinterpret_cast<uint32_t*>(h->fresh_q + h->fresh_ring);
-        a.fq_mask = (uint32_t)h->fresh_ring - 1u;
+    a.rc_obs = L.rc_obs.get();
+    a.rc_rfl = L.rc_rfl.get();
+    a.rc_tag = L.rc_tag.get();
+    a.lane_env = L.lane_env.get();
+    a.wg_scn = L.wg_scn.get();
+    a.scn_tag = h->fresh.scn_tag.get();
+    a.clock = h->clock.get();
+    if (fresh_mode(h) && h->fresh.queue) {
+        a.fq = h->fresh.queue.get();
+        a.fqc = h->fresh.words();
+        a.fq_mask = (uint32_t)h->fresh.ring - 1u;
     }
     return a;
 }
@@ -122,21 +162,21 @@ constexpr int GEN_GRID = 2048;  // K5b workgroups
 hipError_t fresh_regen(d2d_t* h, hipStream_t stream, bool restore = false, bool queued = false) {
     FreshArgs f{};
     f.n = h->n;
-    f.ist = h->ist;
-    f.env_scn = h->env_scn;
+    f.ist = h->lay.ist.get();
+    f.env_scn = h->env_scn.get();
     f.cur = h->cur;
     f.W = h->cfg.screen_w;
     f.H = h->cfg.screen_h;
     f.seed = h->seed;
     f.env_id_base = (uint32_t)h->cfg.env_id_base;
-    f.abi = h->abi;
-    f.scn = static_cast<d2d::ScnR*>(h->scn);  // (fresh mode: h->rm)
-    f.tag = h->scn_tag;
-    f.gclk = h->gclk;
-    f.clock = h->clock;
-    f.queue = h->fresh_q;
-    f.ring = reinterpret_cast<uint32_t*>(h->fresh_q + h->fresh_ring);
-    f.mask = (uint32_t)h->fresh_ring - 1u;
+    f.abi = h->tab.abi.get();
+    f.scn = reinterpret_cast<d2d::ScnR*>(h->tab.scn.get());  // (fresh mode: tab.rm)
+    f.tag = h->fresh.scn_tag.get();
+    f.gclk = h->fresh.gclk.get();
+    f.clock = h->clock.get();
+    f.queue = h->fresh.queue.get();
+    f.ring = h->fresh.words();
+    f.mask = (uint32_t)h->fresh.ring - 1u;
     f.scan = queued ? 0 : 1;
     f.restore = restore ? 1 : 0;
 #ifdef D2D_GEN_STAMPS
@@ -154,23 +194,87 @@ hipError_t fresh_regen(d2d_t* h, hipStream_t stream, bool restore = false, bool 
     hipLaunchKernelGGL(d2d_fresh_tail_kernel, dim3(1), dim3(64), 0, stream, f.ring);
     return hipGetLastError();
 }
-bool fresh_mode(const d2d_t* h) { return h->cfg.scn_pool == 2; }
 size_t ring_size(size_t slots) {  // FreshRing: a power of two holding every slot
     size_t r = 64;
     while (r < slots) r <<= 1;
     return r;
 }
 
-// The scenario table's layout (d2d_device.h ScnF / ScnR): ScnR exactly when K1 will read it from
-// global memory -- the fresh curriculum, and tables too big to stage (pools) unless the map is grouped
-// (a grouped workgroup stages only its own scenarios).  d2d_step dispatches on the same rule.
-bool table_rm(bool fresh, bool grouped, size_t n_total) {
-    if (fresh) return true;
-    if (grouped) return false;
-    return sizeof(d2d::ScnF) * n_total + sizeof(K1Shared) > K1_LDS_BUDGET;
-}
+// Table placement: the one decision of where the kernels read the scenario table from, and so the
+// table's layout (d2d_device.h ScnF / ScnR) and the K1 / K2 / K4 instantiations to launch.  The setters
+// build the table in the layout it names; the launchers launch what it names.
+using StepKernel = void (*)(StepArgs);
+// K1 [LDS][LTAB][S3]; <false, true, *> is never chosen and not instantiated
+constexpr StepKernel K1[2][2][2] = {
+    {{d2d_step_kernel<false, false, false>, d2d_step_kernel<false, false, true>}, {nullptr, nullptr}},
+    {{d2d_step_kernel<true, false, false>, d2d_step_kernel<true, false, true>},
+     {d2d_step_kernel<true, true, false>, d2d_step_kernel<true, true, true>}}};
+constexpr StepKernel K1_GROUPED[2] = {d2d_step_grouped_kernel<false>, d2d_step_grouped_kernel<true>};  // [S3]
+constexpr StepKernel K2[2][2] = {{d2d_reset_kernel<false, false>, d2d_reset_kernel<false, true>},  // [LDS][RM]
+                                 {d2d_reset_kernel<true, false>, d2d_reset_kernel<true, true>}};
+constexpr StepKernel K4[2][2] = {{d2d_fill_kernel<false, false>, d2d_fill_kernel<false, true>},  // [LDS][RM]
+                                 {d2d_fill_kernel<true, false>, d2d_fill_kernel<true, true>}};
+static_assert(sizeof(d2d::ScnF) + sizeof(d2d::BtHot) + sizeof(K1Shared) <= K1_LDS_BUDGET, "grouped K1 LDS");
+static_assert(sizeof(K1Shared) + K1_KN_BYTES <= K1_LDS_BUDGET, "K1 LDS with the staged knots");
+struct Placement {
+    bool rm;               // ScnR: K1 reads the table from global memory.  ScnF: it is staged in LDS
+    const StepKernel* k1;  // [S3]
+    StepKernel k2, k4;
+    size_t k1_lds, k2_lds, k4_lds;  // dynamic LDS
+};
 size_t scn_size(bool rm) { return rm ? sizeof(d2d::ScnR) : sizeof(d2d::ScnF); }
-void* scn_at(const d2d_t* h, size_t k) { return static_cast<char*>(h->scn) + k * scn_size(h->rm); }
+// fresh: the fresh curriculum; grouped: the scenario-grouped slot layout; n_total: table entries;
+// brt: the table has golden-march tables
+Placement place(bool fresh, bool grouped, size_t n_total, bool brt) {
+    Placement p{};
+    const size_t scnf = sizeof(d2d::ScnF) * n_total, hot = sizeof(d2d::BtHot) * n_total;
+    // ScnR exactly when K1 will read the table from global memory: the fresh curriculum, and tables
+    // too big to stage (pools) unless the map is grouped (a grouped workgroup stages only its own scenarios)
+    p.rm = fresh || (!grouped && scnf + sizeof(K1Shared) > K1_LDS_BUDGET);
+    if (grouped) {
+        p.k1 = K1_GROUPED;
+        p.k1_lds = sizeof(d2d::ScnF) + sizeof(d2d::BtHot);
+    } else if (p.rm) {
+        // the plain search's staged knots only without golden-march tables (fresh curriculum);
+        // a pool's tables take the table path, which never reads them
+        p.k1 = K1[0][0];
+        p.k1_lds = brt ? 0 : K1_KN_BYTES;
+    } else {
+        const bool ltab = brt && scnf + hot + sizeof(K1Shared) <= K1_LDS_BUDGET;  // the probe tables fit too
+        p.k1 = K1[1][ltab];
+        p.k1_lds = scnf + (ltab ? hot : 0);
+    }
+    // K2 and K4 stage the whole table when it fits; K4's dynamic LDS is padded to K1's per-workgroup
+    // LDS, so K4 is resident 4 per CU as K1 (d2d_fill_kernel)
+    const size_t table = scn_size(p.rm) * n_total;
+    const size_t pad = sizeof(d2d::ScnF) + sizeof(d2d::BtHot) + sizeof(K1Shared) - 2048;
+    const bool lds = table <= K2_LDS_BUDGET;
+    p.k2 = K2[lds][p.rm];
+    p.k2_lds = lds ? table : 0;
+    p.k4 = K4[lds][p.rm];
+    p.k4_lds = lds ? std::max(table, pad) : pad;
+    return p;
+}
+Placement place(const d2d_t* h) {
+    return place(fresh_mode(h), h->lay.grouped(), (size_t)h->tab.n_scn, h->tab.brt != nullptr);
+}
+void launch(StepKernel k, unsigned grid, int threads, size_t lds, hipStream_t stream, const StepArgs& a) {
+    hipLaunchKernelGGL(k, dim3(grid), dim3(threads), lds, stream, a);
+}
+
+unsigned char* scn_at(const d2d_t* h, size_t k) { return h->tab.scn.get() + k * scn_size(h->tab.rm); }
+// What is wrong with a scenario record, or null; entries with use[k] false are not looked at.
+const char* scn_invalid(const d2d_scn* s, size_t n, const std::vector<bool>* use = nullptr) {
+    for (size_t k = 0; k < n; ++k) {
+        if (use && !(*use)[k]) continue;
+        if (s[k].n_wps < 3 || s[k].n_wps > D2D_MAX_WPS) return "n_wps out of range [3, D2D_MAX_WPS]";
+        if (s[k].n_circles < 0 || s[k].n_circles > D2D_MAX_CIRCLES) return "n_circles out of range [0, D2D_MAX_CIRCLES]";
+    }
+    return nullptr;
+}
+bool map_in_range(const int32_t* env_scn, int n, int n_scn) {
+    return std::all_of(env_scn, env_scn + n, [=](int32_t v) { return v >= 0 && v < n_scn; });
+}
 // host tables in either layout; entries with use(k) false stay zero.  False: a scenario scn_build refuses
 template <class S>
 bool build_tables_t(const d2d_scn* src, size_t n, std::vector<unsigned char>& out, const std::vector<bool>* use) {
@@ -194,148 +298,18 @@ void launch_brtab(bool rm, const void* scn, int n, d2d::BrTab* out) {
 hipError_t rc_fill(d2d_t* h, hipStream_t stream, bool force = false) {
     StepArgs a = make_args(h);
     a.fill_force = force ? 1 : 0;
-    const dim3 grid((h->ns + FILL_SPB - 1) / FILL_SPB);
-    // dynamic LDS padded to K1's per-workgroup LDS, so K4 is resident 4 per CU as K1 (d2d_fill_kernel)
-    const size_t pad = sizeof(d2d::ScnF) + sizeof(d2d::BtHot) + sizeof(K1Shared) - 2048;
-    const size_t lds = scn_size(h->rm) * (size_t)h->n_scn;
-    if (lds <= K2_LDS_BUDGET) {
-        if (h->rm) hipLaunchKernelGGL((d2d_fill_kernel<true, true>), grid, dim3(BLOCK), std::max(lds, pad), stream, a);
-        else hipLaunchKernelGGL((d2d_fill_kernel<true, false>), grid, dim3(BLOCK), std::max(lds, pad), stream, a);
-    } else {
-        if (h->rm) hipLaunchKernelGGL((d2d_fill_kernel<false, true>), grid, dim3(BLOCK), pad, stream, a);
-        else hipLaunchKernelGGL((d2d_fill_kernel<false, false>), grid, dim3(BLOCK), pad, stream, a);
-    }
+    const Placement p = place(h);
+    launch(p.k4, (unsigned)(h->lay.ns + FILL_SPB - 1) / FILL_SPB, BLOCK, p.k4_lds, stream, a);
     return hipGetLastError();
 }
 // drop every entry (new seed, counters or scenarios) and refill, ordered on `stream`
 hipError_t rc_rebuild(d2d_t* h, hipStream_t stream) {
-    hipError_t e = hipMemsetAsync(h->rc_tag, 0xFF, sizeof(int32_t) * RC_SLOTS * (size_t)h->ns, stream);
+    hipError_t e = hipMemsetAsync(h->lay.rc_tag.get(), 0xFF, sizeof(int32_t) * RC_SLOTS * (size_t)h->lay.ns, stream);
     if (e == hipSuccess) e = rc_fill(h, stream, true);
     if (e == hipSuccess) h->rc_dirty = false;
     return e;
 }
 
-// Scenario-grouped slot layout for a static env -> scenario map with several scenarios: each K1
-// workgroup then steps 64 envs of ONE scenario (no per-lane scenario divergence in the Brent
-// search, one scenario + probe table staged in LDS) whose state is contiguous.  The envs, sorted
-// by (scenario, id), are cut into ceil(n / 64) groups -- no padding between scenarios, so the grid
-// is no larger than the identity layout's (at 65 536 envs: 1 024 workgroups = one resident round)
-// and at most n_scn - 1 groups straddle scenarios: wg_scn = -(s + 2) for a group of scenarios s and
-// s + 1 (K1 stages both scenarios in LDS; their probe tables are read through L1/L2), -1 for a group
-// of three or more (everything through L1/L2).  Groups are then
-// ordered by their first env id, so groups whose envs interleave (e.g. scenario = id mod 7) get
-// consecutive numbers (xcd_group places consecutive numbers on one XCD).
-constexpr double STRADDLE_W = 1.25;  // balance_groups: a straddling group's cost over its heavier scenario's
-// host copy of the kernels' block -> group numbering (d2d_kernels.h xcd_group)
-int xcd_group_host(int b, int nb) {
-    const int per = nb / 8, rem = nb % 8, x = b % 8, k = b / 8;
-    return (x < rem) ? x * (per + 1) + k : rem * (per + 1) + (x - rem) * per + k;
-}
-// Co-residency balance (mixed batches).  When every workgroup of K1 is resident at once (ng <= 4 x
-// CUs), the dispatcher fills the CUs round by round in one fixed CU order, so blocks b, b + n_cu,
-// b + 2 n_cu, ... share a CU (measured on MI355X: blocks congruent mod 256 share a CU, in every step
-// of a replayed graph, tools/cu_map.py).  A step lasts as long as its slowest workgroup, and a heavy
-// scenario's workgroup slows down when its CU also runs other heavy ones, so the groups of each XCD's
-// chunk (xcd_group keeps a chunk of consecutive group numbers on one XCD) are dealt over the chunk's
-// CUs by cost, heaviest first onto the least-loaded CU (straddling groups count 1.25 x their heavier
-// scenario).  Renumbers the groups (lanes / ws) in place; the arithmetic is unchanged.
-void balance_groups(int n_cu, const double* cost, int n_cost, std::vector<int32_t>& lanes, std::vector<int32_t>& ws) {
-    const int ng = (int)ws.size();
-    if (n_cu <= 0 || n_cu % 8 != 0 || ng > 4 * n_cu || ng < 2) return;
-    double cmax = 0.0;
-    for (int k = 0; k < n_cost; ++k) cmax = std::max(cmax, cost[k]);
-    auto c = [&](int sc) { return (sc >= 0 && sc < n_cost) ? cost[sc] : cmax; };
-    auto gcost = [&](int g) {
-        const int w = ws[(size_t)g];
-        return w >= 0 ? c(w) : (w <= -2 ? STRADDLE_W * std::max(c(-w - 2), c(-w - 1)) : 1.5 * cmax);
-    };
-    std::vector<int32_t> block_of((size_t)ng);  // group number -> the block that runs it
-    for (int b = 0; b < ng; ++b) block_of[(size_t)xcd_group_host(b, ng)] = b;
-    std::vector<int32_t> newnum((size_t)ng, -1);
-    const int per = ng / 8, rem = ng % 8;
-    for (int x = 0, first = 0; x < 8; ++x) {
-        const int cnt = per + (x < rem ? 1 : 0);
-        // the chunk's positions grouped by CU, each CU's positions in dispatch order
-        std::vector<std::pair<int, int>> pos;  // (cu, position)
-        for (int p = first; p < first + cnt; ++p) pos.emplace_back(block_of[(size_t)p] % n_cu, p);
-        std::stable_sort(pos.begin(), pos.end(), [&](const std::pair<int, int>& u, const std::pair<int, int>& v) {
-            return u.first != v.first ? u.first < v.first : block_of[(size_t)u.second] < block_of[(size_t)v.second];
-        });
-        std::vector<int> cus;
-        std::vector<std::vector<int>> free_pos;
-        for (const auto& q : pos) {
-            if (cus.empty() || cus.back() != q.first) {
-                cus.push_back(q.first);
-                free_pos.emplace_back();
-            }
-            free_pos.back().push_back(q.second);
-        }
-        std::vector<double> load(cus.size(), 0.0);
-        std::vector<size_t> used(cus.size(), 0);
-        std::vector<int> gs;
-        for (int g = first; g < first + cnt; ++g) gs.push_back(g);
-        std::stable_sort(gs.begin(), gs.end(), [&](int u, int v) { return gcost(u) > gcost(v); });
-        for (int g : gs) {
-            size_t best = cus.size();
-            for (size_t k = 0; k < cus.size(); ++k)
-                if (used[k] < free_pos[k].size() && (best == cus.size() || load[k] < load[best])) best = k;
-            newnum[(size_t)g] = free_pos[best][used[best]++];
-            load[best] += gcost(g);
-        }
-        first += cnt;
-    }
-    std::vector<int32_t> l2(lanes.size(), -1), w2((size_t)ng, 0);
-    for (int g = 0; g < ng; ++g) {
-        const size_t d = (size_t)newnum[(size_t)g];
-        w2[d] = ws[(size_t)g];
-        for (int l = 0; l < EPB; ++l) l2[d * EPB + (size_t)l] = lanes[(size_t)g * EPB + (size_t)l];
-    }
-    lanes.swap(l2);
-    ws.swap(w2);
-}
-
-void make_groups(int n, const int32_t* env_scn, int n_scn, std::vector<int32_t>& lanes, std::vector<int32_t>& ws) {
-    std::vector<int32_t> order((size_t)n);
-    for (int i = 0; i < n; ++i) order[(size_t)i] = i;
-    std::stable_sort(order.begin(), order.end(), [&](int32_t x, int32_t y) { return env_scn[x] < env_scn[y]; });
-    const size_t ng = ((size_t)n + EPB - 1) / EPB;
-    std::vector<size_t> gi(ng);
-    for (size_t g = 0; g < ng; ++g) gi[g] = g;
-    std::sort(gi.begin(), gi.end(), [&](size_t x, size_t y) { return order[x * EPB] < order[y * EPB]; });
-    lanes.assign(ng * EPB, -1);
-    ws.assign(ng, 0);
-    for (size_t g = 0; g < ng; ++g) {
-        const size_t o = gi[g] * EPB;
-        const int32_t lo = env_scn[order[o]];
-        int32_t hi = lo;
-        for (size_t l = 0; l < EPB && o + l < (size_t)n; ++l) {
-            lanes[g * EPB + l] = order[o + l];
-            hi = std::max(hi, env_scn[order[o + l]]);
-        }
-        // pure: the scenario; straddling exactly two consecutive scenarios: -(lo + 2); more: -1
-        ws[g] = hi == lo ? lo : (hi == lo + 1 ? -(lo + 2) : -1);
-    }
-}
-
-// Internal arrays of one slot layout.
-struct Layout {
-    int ns = 0;
-    double* st = nullptr;
-    int32_t* ist = nullptr;
-    double* acc = nullptr;
-    float* rc_obs = nullptr;
-    int32_t* rc_rfl = nullptr;
-    int32_t* rc_tag = nullptr;
-    int32_t* lane_env = nullptr;
-    int32_t* wg_scn = nullptr;
-    int32_t* env_slot = nullptr;
-};
-void free_layout(Layout& L) {
-    for (void* p : {(void*)L.st, (void*)L.ist, (void*)L.acc, (void*)L.rc_obs, (void*)L.rc_rfl, (void*)L.rc_tag,
-                    (void*)L.lane_env, (void*)L.wg_scn, (void*)L.env_slot})
-        if (p) (void)hipFree(p);
-    L = Layout{};
-}
 // allocate a layout of n envs: identity (lanes empty) or grouped (lanes: slot -> env, ws: scenario
 // per group); state zeroed, reset cache empty
 hipError_t alloc_layout(Layout& L, int n, const std::vector<int32_t>& lanes, const std::vector<int32_t>& ws) {
@@ -343,61 +317,19 @@ hipError_t alloc_layout(Layout& L, int n, const std::vector<int32_t>& lanes, con
     L.ns = lanes.empty() ? n : (int)lanes.size();
     const size_t ns = (size_t)L.ns;
     hipError_t e;
-    if ((e = hipMalloc(&L.st, sizeof(double) * D2D_NSTATE * ns)) != hipSuccess ||
-        (e = hipMalloc(&L.ist, sizeof(int32_t) * D2D_NISTATE * ns)) != hipSuccess ||
-        (e = hipMalloc(&L.acc, sizeof(double) * D2D_NSTATS * ns)) != hipSuccess ||
-        (e = hipMalloc(&L.rc_obs, sizeof(float) * D2D_OBS_DIM * RC_SLOTS * ns)) != hipSuccess ||
-        (e = hipMalloc(&L.rc_rfl, sizeof(int32_t) * RC_SLOTS * ns)) != hipSuccess ||
-        (e = hipMalloc(&L.rc_tag, sizeof(int32_t) * RC_SLOTS * ns)) != hipSuccess ||
-        (e = hipMemset(L.st, 0, sizeof(double) * D2D_NSTATE * ns)) != hipSuccess ||
-        (e = hipMemset(L.ist, 0, sizeof(int32_t) * D2D_NISTATE * ns)) != hipSuccess ||
-        (e = hipMemset(L.acc, 0, sizeof(double) * D2D_NSTATS * ns)) != hipSuccess ||
-        (e = hipMemset(L.rc_tag, 0xFF, sizeof(int32_t) * RC_SLOTS * ns)) != hipSuccess) {
-        free_layout(L);
+    if ((e = dev_new(L.st, D2D_NSTATE * ns)) != hipSuccess || (e = dev_new(L.ist, D2D_NISTATE * ns)) != hipSuccess ||
+        (e = dev_new(L.acc, D2D_NSTATS * ns)) != hipSuccess ||
+        (e = dev_new(L.rc_obs, D2D_OBS_DIM * RC_SLOTS * ns)) != hipSuccess ||
+        (e = dev_new(L.rc_rfl, RC_SLOTS * ns)) != hipSuccess || (e = dev_new(L.rc_tag, RC_SLOTS * ns, 0xFF)) != hipSuccess ||
+        lanes.empty())
         return e;
-    }
-    if (!lanes.empty()) {
-        std::vector<int32_t> es((size_t)n, 0);
-        for (size_t k = 0; k < lanes.size(); ++k)
-            if (lanes[k] >= 0) es[(size_t)lanes[k]] = (int32_t)k;
-        if ((e = hipMalloc(&L.lane_env, sizeof(int32_t) * ns)) != hipSuccess ||
-            (e = hipMalloc(&L.wg_scn, sizeof(int32_t) * ws.size())) != hipSuccess ||
-            (e = hipMalloc(&L.env_slot, sizeof(int32_t) * (size_t)n)) != hipSuccess ||
-            (e = hipMemcpy(L.lane_env, lanes.data(), sizeof(int32_t) * ns, hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy(L.wg_scn, ws.data(), sizeof(int32_t) * ws.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy(L.env_slot, es.data(), sizeof(int32_t) * (size_t)n, hipMemcpyHostToDevice)) != hipSuccess) {
-            free_layout(L);
-            return e;
-        }
-    }
-    return hipSuccess;
-}
-Layout take_layout(d2d_t* h) {
-    Layout L;
-    L.ns = h->ns;
-    L.st = h->st;
-    L.ist = h->ist;
-    L.acc = h->acc;
-    L.rc_obs = h->rc_obs;
-    L.rc_rfl = h->rc_rfl;
-    L.rc_tag = h->rc_tag;
-    L.lane_env = h->lane_env;
-    L.wg_scn = h->wg_scn;
-    L.env_slot = h->env_slot;
-    return L;
-}
-void put_layout(d2d_t* h, const Layout& L) {
-    h->ns = L.ns;
-    h->st = L.st;
-    h->ist = L.ist;
-    h->acc = L.acc;
-    h->rc_obs = L.rc_obs;
-    h->rc_rfl = L.rc_rfl;
-    h->rc_tag = L.rc_tag;
-    h->lane_env = L.lane_env;
-    h->wg_scn = L.wg_scn;
-    h->env_slot = L.env_slot;
-    h->n_groups = L.lane_env ? L.ns / EPB : 0;
+    std::vector<int32_t> es((size_t)n, 0);
+    for (size_t k = 0; k < lanes.size(); ++k)
+        if (lanes[k] >= 0) es[(size_t)lanes[k]] = (int32_t)k;
+    if ((e = dev_new(L.lane_env, ns, 0, lanes.data(), ns)) != hipSuccess ||
+        (e = dev_new(L.wg_scn, ws.size(), 0, ws.data(), ws.size())) != hipSuccess)
+        return e;
+    return dev_new(L.env_slot, (size_t)n, 0, es.data(), (size_t)n);
 }
 // every env's state, flags and accumulators from layout `from` to layout `to` (stream-ordered)
 template <typename T>
@@ -408,12 +340,35 @@ hipError_t permute(const T* src, int sstride, const int32_t* sslot, T* dst, int 
     return hipGetLastError();
 }
 hipError_t move_state(const Layout& from, const Layout& to, int n) {
+    const int32_t *fs = from.env_slot.get(), *ts = to.env_slot.get();
     hipError_t e;
-    if ((e = permute(from.st, from.ns, from.env_slot, to.st, to.ns, to.env_slot, D2D_NSTATE, n, 0)) != hipSuccess ||
-        (e = permute(from.ist, from.ns, from.env_slot, to.ist, to.ns, to.env_slot, D2D_NISTATE, n, 0)) != hipSuccess ||
-        (e = permute(from.acc, from.ns, from.env_slot, to.acc, to.ns, to.env_slot, D2D_NSTATS, n, 0)) != hipSuccess)
+    if ((e = permute(from.st.get(), from.ns, fs, to.st.get(), to.ns, ts, D2D_NSTATE, n, 0)) != hipSuccess ||
+        (e = permute(from.ist.get(), from.ns, fs, to.ist.get(), to.ns, ts, D2D_NISTATE, n, 0)) != hipSuccess ||
+        (e = permute(from.acc.get(), from.ns, fs, to.acc.get(), to.ns, ts, D2D_NSTATS, n, 0)) != hipSuccess)
         return e;
     return hipDeviceSynchronize();
+}
+// Put the running batch into the slot layout (lanes, ws) -- the identity when lanes is empty: allocate,
+// move every env's state across, swap the layouts, free the old one.  A failure leaves the handle as it was.
+hipError_t relayout(d2d_t* h, const std::vector<int32_t>& lanes, const std::vector<int32_t>& ws) {
+    Layout to;
+    hipError_t e = alloc_layout(to, h->n, lanes, ws);
+    if (e == hipSuccess) e = move_state(h->lay, to, h->n);
+    if (e != hipSuccess) return e;
+    std::swap(h->lay, to);
+    h->stale();  // captured graphs hold the old layout's buffers; the reset cache starts empty
+    return hipSuccess;
+}
+// one state array between the handle's slot order and the caller's env order (to_env: out of the
+// handle); an array the caller did not pass is skipped
+template <typename T>
+hipError_t copy_state(const d2d_t* h, bool to_env, const T* src, T* dst, int nf, hipStream_t s) {
+    if (!src || !dst) return hipSuccess;
+    const Layout& L = h->lay;
+    if (!L.grouped()) return hipMemcpyAsync(dst, src, sizeof(T) * (size_t)nf * (size_t)h->n, hipMemcpyDeviceToDevice, s);
+    const int32_t *none = nullptr, *slot = L.env_slot.get();
+    return to_env ? permute(src, L.ns, slot, dst, h->n, none, nf, h->n, s)
+                  : permute(src, h->n, none, dst, L.ns, slot, nf, h->n, s);
 }
 
 struct DeviceGuard {
@@ -426,6 +381,18 @@ struct DeviceGuard {
         if (prev >= 0) (void)hipSetDevice(prev);
     }
 };
+
+// d2d_group_layout / d2d_balanced_group_layout (cost null: the natural order)
+int32_t group_layout(const char* who, int32_t n, const int32_t* env_scn, int32_t n_scn, const double* cost, int32_t n_cu,
+                     int32_t* slot_env, int32_t* group_scn) {
+    if (!map_in_range(env_scn, n, n_scn)) return fail(D2D_E_ARG, std::string(who) + ": env scenario index out of range"), -1;
+    std::vector<int32_t> lanes, ws;
+    make_groups(n, env_scn, lanes, ws);
+    if (cost) balance_groups(n_cu, cost, n_scn, lanes, ws);
+    std::copy(lanes.begin(), lanes.end(), slot_env);
+    std::copy(ws.begin(), ws.end(), group_scn);
+    return (int32_t)ws.size();
+}
 
 }  // namespace
 
@@ -442,50 +409,24 @@ int32_t d2d_create(const d2d_cfg* cfg, int32_t n_envs, int32_t device, d2d_t** o
     if (e != hipSuccess) return hip_fail(e, "hipGetDeviceCount");
     if (device < 0 || device >= ndev) return fail(D2D_E_ARG, "d2d_create: bad device index");
     DeviceGuard g(device);
-    d2d_t* h = new (std::nothrow) d2d_t();
+    std::unique_ptr<d2d_t> h(new (std::nothrow) d2d_t());
     if (!h) return fail(D2D_E_NOMEM, "d2d_create: host allocation failed");
     h->cfg = *cfg;
     h->n = n_envs;
     h->device = device;
     if (hipDeviceGetAttribute(&h->n_cu, hipDeviceAttributeMultiprocessorCount, device) != hipSuccess) h->n_cu = 256;
-    const size_t n = (size_t)n_envs;
-    Layout L;
-    if ((e = hipMalloc(&h->env_scn, sizeof(int32_t) * n)) != hipSuccess ||
-        (e = hipMalloc(&h->pool_dev, sizeof(int32_t))) != hipSuccess ||
-        (e = hipMemset(h->pool_dev, 0, sizeof(int32_t))) != hipSuccess ||
-        (e = hipMalloc(&h->fill_ctl, 2 * sizeof(int32_t))) != hipSuccess ||
-        (e = hipMemset(h->fill_ctl, 0, 2 * sizeof(int32_t))) != hipSuccess ||
-        (e = hipMalloc(&h->clock, sizeof(int64_t))) != hipSuccess ||
-        (e = hipMemset(h->clock, 0, sizeof(int64_t))) != hipSuccess ||
-        (e = alloc_layout(L, n_envs, {}, {})) != hipSuccess) {
-        d2d_destroy(h);
+    if ((e = dev_new(h->env_scn, (size_t)n_envs)) != hipSuccess || (e = dev_new(h->pool_dev, 1)) != hipSuccess ||
+        (e = dev_new(h->fill_ctl, 2)) != hipSuccess || (e = dev_new(h->clock, 1)) != hipSuccess ||
+        (e = alloc_layout(h->lay, n_envs, {}, {})) != hipSuccess)
         return hip_fail(e, "d2d_create: hipMalloc");
-    }
-    put_layout(h, L);
-    (void)hipMemset(h->env_scn, 0, sizeof(int32_t) * n);
-    if ((e = hipDeviceSynchronize()) != hipSuccess) {
-        d2d_destroy(h);
-        return hip_fail(e, "d2d_create: memset");
-    }
-    *out = h;
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail(e, "d2d_create: memset");
+    *out = h.release();
     return D2D_OK;
 }
 
 void d2d_destroy(d2d_t* h) {
     if (!h) return;
     DeviceGuard g(h->device);
-    Layout L = take_layout(h);
-    free_layout(L);
-    if (h->scn) (void)hipFree(h->scn);
-    if (h->brt) (void)hipFree(h->brt);
-    if (h->env_scn) (void)hipFree(h->env_scn);
-    if (h->pool_dev) (void)hipFree(h->pool_dev);
-    if (h->fill_ctl) (void)hipFree(h->fill_ctl);
-    if (h->clock) (void)hipFree(h->clock);
-    if (h->abi) (void)hipFree(h->abi);
-    if (h->scn_tag) (void)hipFree(h->scn_tag);
-    if (h->gclk) (void)hipFree(h->gclk);
-    if (h->fresh_q) (void)hipFree(h->fresh_q);
     delete h;
 }
 
@@ -515,95 +456,54 @@ int32_t d2d_debug_bstamps(uint64_t* out, int32_t clear) {
 int32_t d2d_set_scenarios(d2d_t* h, const d2d_scn* scns, int32_t n_scn, const int32_t* env_scn_host) {
     if (!h || !scns || n_scn <= 0) return fail(D2D_E_ARG, "d2d_set_scenarios: null handle/scenarios or n_scn <= 0");
     if (fresh_mode(h)) return fail(D2D_E_ARG, "d2d_set_scenarios: fresh curriculum mode (cfg.scn_pool = 2) uses d2d_set_curriculum");
-    for (int k = 0; k < n_scn; ++k) {
-        const d2d_scn& s = scns[k];
-        if (s.n_wps < 3 || s.n_wps > D2D_MAX_WPS)
-            return fail(D2D_E_ARG, "d2d_set_scenarios: n_wps out of range [3, D2D_MAX_WPS]");
-        if (s.n_circles < 0 || s.n_circles > D2D_MAX_CIRCLES)
-            return fail(D2D_E_ARG, "d2d_set_scenarios: n_circles out of range [0, D2D_MAX_CIRCLES]");
-    }
-    if (env_scn_host) {
-        for (int i = 0; i < h->n; ++i)
-            if (env_scn_host[i] < 0 || env_scn_host[i] >= n_scn)
-                return fail(D2D_E_ARG, "d2d_set_scenarios: env scenario index out of range");
-    }
+    if (const char* why = scn_invalid(scns, (size_t)n_scn)) return fail(D2D_E_ARG, std::string("d2d_set_scenarios: ") + why);
+    if (env_scn_host && !map_in_range(env_scn_host, h->n, n_scn))
+        return fail(D2D_E_ARG, "d2d_set_scenarios: env scenario index out of range");
     // validate and build everything before touching the handle: a bad scenario leaves it as it was
     // pool mode: room for a second pool half (d2d_refresh_pool), zero until the first refresh
     const size_t T = (size_t)n_scn * (h->cfg.scn_pool ? 2 : 1);
+    // slot layout: grouped for a static mixed map (pool mode redraws scenarios at every reset)
     const bool grouped = env_scn_host && n_scn > 1 && !h->cfg.scn_pool;
-    const bool rm = table_rm(false, grouped, T);
-    std::vector<unsigned char> tab;
-    if (!build_tables(rm, scns, (size_t)n_scn, tab))
+    ScnTables tab;
+    tab.n_scn = (int)T;
+    tab.rm = place(false, grouped, T, true).rm;
+    std::vector<unsigned char> host;
+    if (!build_tables(tab.rm, scns, (size_t)n_scn, host))
         return fail(D2D_E_ARG, "d2d_set_scenarios: us[n_wps-2] - us[n_wps-3] must exceed 0.001");
     DeviceGuard g(h->device);
     hipError_t e;
-    void* scn = nullptr;
-    d2d::BrTab* brt = nullptr;
-    d2d_scn* abi = nullptr;
-    auto drop = [&](hipError_t err, const char* what) {
-        if (scn) (void)hipFree(scn);
-        if (brt) (void)hipFree(brt);
-        if (abi) (void)hipFree(abi);
-        return hip_fail(err, what);
-    };
-    const size_t sz = scn_size(rm);
-    if ((e = hipMalloc(&scn, sz * T)) != hipSuccess) return drop(e, "hipMalloc scn");
-    if ((e = hipMemset(scn, 0, sz * T)) != hipSuccess) return drop(e, "hipMemset scn");
-    if ((e = hipMemcpy(scn, tab.data(), tab.size(), hipMemcpyHostToDevice)) != hipSuccess) return drop(e, "hipMemcpy scn");
-    if (h->cfg.scn_pool) {  // pool mode keeps the ABI records for checkpoints / readback
-        if ((e = hipMalloc(&abi, sizeof(d2d_scn) * T)) != hipSuccess) return drop(e, "hipMalloc abi");
-        if ((e = hipMemset(abi, 0, sizeof(d2d_scn) * T)) != hipSuccess) return drop(e, "hipMemset abi");
-        if ((e = hipMemcpy(abi, scns, sizeof(d2d_scn) * (size_t)n_scn, hipMemcpyHostToDevice)) != hipSuccess)
-            return drop(e, "hipMemcpy abi");
-    }
+    if ((e = dev_new(tab.scn, scn_size(tab.rm) * T, 0, host.data(), host.size())) != hipSuccess)
+        return hip_fail(e, "hipMalloc scn");
+    // pool mode keeps the ABI records for checkpoints / readback
+    if (h->cfg.scn_pool && (e = dev_new(tab.abi, T, 0, scns, (size_t)n_scn)) != hipSuccess) return hip_fail(e, "hipMalloc abi");
     // golden-march tables: forced searches on the device (same arithmetic as the step kernels)
-    if ((e = hipMalloc(&brt, sizeof(d2d::BrTab) * T)) != hipSuccess) return drop(e, "hipMalloc brt");
-    if ((e = hipMemset(brt, 0, sizeof(d2d::BrTab) * T)) != hipSuccess) return drop(e, "hipMemset brt");
-    launch_brtab(rm, scn, n_scn, brt);
-    if ((e = hipGetLastError()) != hipSuccess) return drop(e, "d2d_brtab_kernel launch");
-    if ((e = hipMemset(h->pool_dev, 0, sizeof(int32_t))) != hipSuccess) return drop(e, "hipMemset pool");
-    if ((e = hipDeviceSynchronize()) != hipSuccess) return drop(e, "d2d_brtab_kernel");
-    // slot layout: grouped for a static mixed map (pool mode redraws scenarios at every reset);
-    // the current state moves into the new layout
+    if ((e = dev_new(tab.brt, T)) != hipSuccess) return hip_fail(e, "hipMalloc brt");
+    launch_brtab(tab.rm, tab.scn.get(), n_scn, tab.brt.get());
+    if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "d2d_brtab_kernel launch");
+    if ((e = hipMemset(h->pool_dev.get(), 0, sizeof(int32_t))) != hipSuccess) return hip_fail(e, "hipMemset pool");
+    if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail(e, "d2d_brtab_kernel");
     std::vector<int32_t> lanes, ws;
     if (grouped) {
-        make_groups(h->n, env_scn_host, n_scn, lanes, ws);
+        make_groups(h->n, env_scn_host, lanes, ws);
         if ((int)h->scn_cost.size() == n_scn) balance_groups(h->n_cu, h->scn_cost.data(), n_scn, lanes, ws);
     }
-    Layout to;
-    const bool relayout = !lanes.empty() || h->lane_env;
-    if (relayout) {
-        if ((e = alloc_layout(to, h->n, lanes, ws)) != hipSuccess) return drop(e, "d2d_set_scenarios: layout");
-        if ((e = move_state(take_layout(h), to, h->n)) != hipSuccess) {
-            free_layout(to);
-            return drop(e, "d2d_set_scenarios: layout move");
-        }
+    // commit: the current state moves into the new layout (the last step that can fail with the
+    // handle intact), then the handle takes the new scenarios
+    if (grouped || h->lay.grouped()) {
+        if ((e = relayout(h, lanes, ws)) != hipSuccess) return hip_fail(e, "d2d_set_scenarios: layout");
+    } else {
+        h->stale();  // the old tables are freed: captured graphs point at them
     }
-    // commit: from here on the handle holds the new scenarios
-    if (relayout) {
-        Layout from = take_layout(h);
-        put_layout(h, to);
-        free_layout(from);
-    }
-    if (h->scn) (void)hipFree(h->scn);
-    if (h->brt) (void)hipFree(h->brt);
-    if (h->abi) (void)hipFree(h->abi);
-    h->scn = scn;
-    h->rm = rm;
-    h->brt = brt;
-    h->abi = abi;
-    h->n_scn = (int)T;
+    h->tab = std::move(tab);
     h->pool_base = 0;
     h->pool_n = n_scn;
     h->pool_valid = 1;
-    h->generation += 1;  // the old tables are freed: captured graphs point at them
-    h->rc_dirty = true;  // cached reset observations belong to the old scenarios
     if ((int)h->scn_cost.size() != n_scn) h->scn_cost.assign((size_t)n_scn, 1.0);
-    e = env_scn_host ? hipMemcpy(h->env_scn, env_scn_host, sizeof(int32_t) * (size_t)h->n, hipMemcpyHostToDevice)
-                     : hipMemset(h->env_scn, 0, sizeof(int32_t) * (size_t)h->n);
+    e = env_scn_host ? hipMemcpy(h->env_scn.get(), env_scn_host, sizeof(int32_t) * (size_t)h->n, hipMemcpyHostToDevice)
+                     : hipMemset(h->env_scn.get(), 0, sizeof(int32_t) * (size_t)h->n);
     if (e != hipSuccess) {
         // the env -> scenario map is unknown: no step or reset until the next d2d_set_scenarios
-        h->n_scn = 0;
+        h->tab.n_scn = 0;
         h->reset_done = false;
         return hip_fail(e, "d2d_set_scenarios: env_scn upload");
     }
@@ -612,55 +512,47 @@ int32_t d2d_set_scenarios(d2d_t* h, const d2d_scn* scns, int32_t n_scn, const in
 
 int32_t d2d_set_scenario_costs(d2d_t* h, const double* cost, int32_t n_scn) {
     if (!h || !cost) return fail(D2D_E_ARG, "d2d_set_scenario_costs: null argument");
-    if (h->cfg.scn_pool || n_scn != h->n_scn) return fail(D2D_E_ARG, "d2d_set_scenario_costs: one cost per scenario (test mode)");
+    if (h->cfg.scn_pool || n_scn != h->tab.n_scn) return fail(D2D_E_ARG, "d2d_set_scenario_costs: one cost per scenario (test mode)");
     for (int k = 0; k < n_scn; ++k)
         if (!(cost[k] >= 0.0)) return fail(D2D_E_ARG, "d2d_set_scenario_costs: costs must be >= 0");
     DeviceGuard g(h->device);
     hipError_t e;
     if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail(e, "d2d_set_scenario_costs: sync");
-    h->scn_cost.assign(cost, cost + n_scn);
-    if (h->lane_env) {
+    if (h->lay.grouped()) {
         // grouped layout: deal the groups over the CUs by the new costs (balance_groups); the state
         // moves into the renumbered layout, the reset cache refills
         std::vector<int32_t> es((size_t)h->n);
-        if ((e = hipMemcpy(es.data(), h->env_scn, sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToHost)) != hipSuccess)
+        if ((e = hipMemcpy(es.data(), h->env_scn.get(), sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToHost)) != hipSuccess)
             return hip_fail(e, "d2d_set_scenario_costs: env_scn");
         std::vector<int32_t> lanes, ws;
-        make_groups(h->n, es.data(), n_scn, lanes, ws);
-        balance_groups(h->n_cu, h->scn_cost.data(), n_scn, lanes, ws);
-        Layout to;
-        if ((e = alloc_layout(to, h->n, lanes, ws)) != hipSuccess) return hip_fail(e, "d2d_set_scenario_costs: layout");
-        if ((e = move_state(take_layout(h), to, h->n)) != hipSuccess) {
-            free_layout(to);
-            return hip_fail(e, "d2d_set_scenario_costs: layout move");
-        }
-        Layout from = take_layout(h);
-        put_layout(h, to);
-        free_layout(from);
-        h->generation += 1;  // captured graphs hold the old layout's buffers
-        h->rc_dirty = true;
+        make_groups(h->n, es.data(), lanes, ws);
+        balance_groups(h->n_cu, cost, n_scn, lanes, ws);
+        if ((e = relayout(h, lanes, ws)) != hipSuccess) return hip_fail(e, "d2d_set_scenario_costs: layout");
     }
+    h->scn_cost.assign(cost, cost + n_scn);
     return D2D_OK;
 }
 
 int32_t d2d_get_group_layout(d2d_t* h, int32_t* slot_env, int32_t* group_scn) {
     if (!h) return fail(D2D_E_ARG, "d2d_get_group_layout: null handle"), -1;
-    if (!h->lane_env) return 0;
+    const Layout& L = h->lay;
+    if (!L.grouped()) return 0;
     if (!slot_env || !group_scn) return fail(D2D_E_ARG, "d2d_get_group_layout: null output"), -1;
     DeviceGuard g(h->device);
     hipError_t e;
     if ((e = hipDeviceSynchronize()) != hipSuccess ||
-        (e = hipMemcpy(slot_env, h->lane_env, sizeof(int32_t) * (size_t)h->ns, hipMemcpyDeviceToHost)) != hipSuccess ||
-        (e = hipMemcpy(group_scn, h->wg_scn, sizeof(int32_t) * (size_t)h->n_groups, hipMemcpyDeviceToHost)) != hipSuccess)
+        (e = hipMemcpy(slot_env, L.lane_env.get(), sizeof(int32_t) * (size_t)L.ns, hipMemcpyDeviceToHost)) != hipSuccess ||
+        (e = hipMemcpy(group_scn, L.wg_scn.get(), sizeof(int32_t) * (size_t)L.n_groups(), hipMemcpyDeviceToHost)) != hipSuccess)
         return hip_fail(e, "d2d_get_group_layout"), -1;
-    return h->n_groups;
+    return L.n_groups();
 }
 
 int32_t d2d_reset(d2d_t* h, const uint8_t* mask_dev, uint64_t seed, float* obs_dev, void* stream) {
     if (!h) return fail(D2D_E_ARG, "d2d_reset: null handle");
-    if (h->n_scn <= 0) return fail(D2D_E_STATE, "d2d_reset: call d2d_set_scenarios first");
+    if (h->tab.n_scn <= 0) return fail(D2D_E_STATE, "d2d_reset: call d2d_set_scenarios first");
     DeviceGuard g(h->device);
     hipError_t e;
+    const hipStream_t rs = (hipStream_t)stream;
     if (fresh_mode(h) && mask_dev && (!h->fresh_seeded || h->fresh_seed != seed))
         return fail(D2D_E_ARG, "d2d_reset: fresh curriculum -- a masked reset must keep the seed of the "
                                "previous full reset");
@@ -670,33 +562,23 @@ int32_t d2d_reset(d2d_t* h, const uint8_t* mask_dev, uint64_t seed, float* obs_d
         // episodes this reset starts.  (A masked reset cannot change the seed, checked above: the
         // envs it leaves running would keep old-seed scenarios no recipe (key, clock) regenerates.)
         if (!h->fresh_seeded || h->fresh_seed != seed) {
-            if ((e = hipMemsetAsync(h->scn_tag, 0xFF, sizeof(int32_t) * 2 * (size_t)h->n, (hipStream_t)stream)) !=
-                hipSuccess)
+            if ((e = hipMemsetAsync(h->fresh.scn_tag.get(), 0xFF, sizeof(int32_t) * 2 * (size_t)h->n, rs)) != hipSuccess)
                 return hip_fail(e, "d2d_reset: fresh slots");
             h->fresh_seed = seed;
             h->fresh_seeded = true;
         }
-        if ((e = fresh_regen(h, (hipStream_t)stream)) != hipSuccess) return hip_fail(e, "d2d_reset: fresh scenarios");
+        if ((e = fresh_regen(h, rs)) != hipSuccess) return hip_fail(e, "d2d_reset: fresh scenarios");
     }
     StepArgs a = make_args(h);
     a.obs = obs_dev;
     a.mask = mask_dev;
-    const dim3 grid((h->ns + BLOCK - 1) / BLOCK);
-    const size_t lds = scn_size(h->rm) * (size_t)h->n_scn;
-    const hipStream_t rs = (hipStream_t)stream;
-    if (lds <= K2_LDS_BUDGET) {
-        if (h->rm) hipLaunchKernelGGL((d2d_reset_kernel<true, true>), grid, dim3(BLOCK), lds, rs, a);
-        else hipLaunchKernelGGL((d2d_reset_kernel<true, false>), grid, dim3(BLOCK), lds, rs, a);
-    } else {
-        if (h->rm) hipLaunchKernelGGL((d2d_reset_kernel<false, true>), grid, dim3(BLOCK), 0, rs, a);
-        else hipLaunchKernelGGL((d2d_reset_kernel<false, false>), grid, dim3(BLOCK), 0, rs, a);
-    }
+    const Placement p = place(h);
+    launch(p.k2, (unsigned)(h->lay.ns + BLOCK - 1) / BLOCK, BLOCK, p.k2_lds, rs, a);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "d2d_reset launch");
-    if (fresh_mode(h) && (e = fresh_regen(h, (hipStream_t)stream)) != hipSuccess)
-        return hip_fail(e, "d2d_reset: fresh scenarios");
+    if (fresh_mode(h) && (e = fresh_regen(h, rs)) != hipSuccess) return hip_fail(e, "d2d_reset: fresh scenarios");
     // cached next-reset observations depend on the seed and the episode counters: drop and refill
-    if ((e = rc_rebuild(h, (hipStream_t)stream)) != hipSuccess) return hip_fail(e, "d2d_reset: cache rebuild");
+    if ((e = rc_rebuild(h, rs)) != hipSuccess) return hip_fail(e, "d2d_reset: cache rebuild");
     h->reset_done = true;
     return D2D_OK;
 }
@@ -705,12 +587,12 @@ int32_t d2d_step(d2d_t* h, const float* act_dev, float* obs_dev, float* rew_dev,
                  uint8_t* trunc_dev, float* info_dev, float* term_obs_dev, void* stream) {
     if (!h || !act_dev || !obs_dev || !rew_dev || !term_dev || !trunc_dev)
         return fail(D2D_E_ARG, "d2d_step: null handle or required buffer");
-    if (h->n_scn <= 0 || !h->reset_done) return fail(D2D_E_STATE, "d2d_step: call d2d_set_scenarios and d2d_reset first");
+    if (h->tab.n_scn <= 0 || !h->reset_done) return fail(D2D_E_STATE, "d2d_step: call d2d_set_scenarios and d2d_reset first");
     if (((uintptr_t)act_dev & 7u) != 0) return fail(D2D_E_ARG, "d2d_step: act_dev must be 8-byte aligned");
     DeviceGuard g(h->device);
     hipError_t e;
-    if (h->rc_dirty && (e = rc_rebuild(h, (hipStream_t)stream)) != hipSuccess)
-        return hip_fail(e, "d2d_step: cache rebuild");
+    const hipStream_t ss = (hipStream_t)stream;
+    if (h->rc_dirty && (e = rc_rebuild(h, ss)) != hipSuccess) return hip_fail(e, "d2d_step: cache rebuild");
     StepArgs a = make_args(h);
     a.act = act_dev;
     a.obs = obs_dev;
@@ -719,40 +601,15 @@ int32_t d2d_step(d2d_t* h, const float* act_dev, float* obs_dev, float* rew_dev,
     a.trunc = trunc_dev;
     a.info = info_dev;
     a.tobs = term_obs_dev;
-    const dim3 grid((h->n + EPB - 1) / EPB);
-    const size_t lds_scn = sizeof(d2d::ScnF) * (size_t)h->n_scn, lds_hot = sizeof(d2d::BtHot) * (size_t)h->n_scn;
-    static_assert(sizeof(d2d::ScnF) + sizeof(d2d::BtHot) + sizeof(K1Shared) <= K1_LDS_BUDGET, "grouped K1 LDS");
-    {
-        // the three-way table re-check pays when the SIMDs have idle issue slots (at most one K1
-        // workgroup per CU: 4 096 / 16 384 envs -4 %), not at full load (65 536 envs +3.6 %)
-        const int nwg = h->lane_env ? h->n_groups : (int)grid.x;
-        const bool s3 = nwg <= std::max(h->n_cu, 1);
-        auto launch = [&](auto kern, dim3 g, size_t lds) {
-            hipLaunchKernelGGL(kern, g, dim3(K1_THREADS), lds, (hipStream_t)stream, a);
-        };
-        if (h->lane_env) {
-            const size_t lds = sizeof(d2d::ScnF) + sizeof(d2d::BtHot);
-            if (s3) launch(d2d_step_grouped_kernel<true>, dim3(h->n_groups), lds);
-            else launch(d2d_step_grouped_kernel<false>, dim3(h->n_groups), lds);
-        } else if (!h->rm && a.brt && lds_scn + lds_hot + sizeof(K1Shared) <= K1_LDS_BUDGET) {
-            if (s3) launch(d2d_step_kernel<true, true, true>, grid, lds_scn + lds_hot);
-            else launch(d2d_step_kernel<true, true, false>, grid, lds_scn + lds_hot);
-        } else if (!h->rm) {  // (table_rm: a ScnF table fits K1's LDS)
-            if (s3) launch(d2d_step_kernel<true, false, true>, grid, lds_scn);
-            else launch(d2d_step_kernel<true, false, false>, grid, lds_scn);
-        } else {
-            // the plain search's staged knots only without golden-march tables (fresh curriculum);
-            // a pool's tables (a.brt) take the table path, which never reads them
-            const size_t kn = a.brt ? 0 : K1_KN_BYTES;
-            static_assert(sizeof(K1Shared) + K1_KN_BYTES <= K1_LDS_BUDGET, "K1 LDS with the staged knots");
-            if (s3) launch(d2d_step_kernel<false, false, true>, grid, kn);
-            else launch(d2d_step_kernel<false, false, false>, grid, kn);
-        }
-    }
+    const Placement p = place(h);
+    // the three-way table re-check pays when the SIMDs have idle issue slots (at most one K1
+    // workgroup per CU: 4 096 / 16 384 envs -4 %), not at full load (65 536 envs +3.6 %)
+    const int nwg = h->lay.grouped() ? h->lay.n_groups() : (h->n + EPB - 1) / EPB;
+    const bool s3 = nwg <= std::max(h->n_cu, 1);
+    launch(p.k1[s3], (unsigned)nwg, K1_THREADS, p.k1_lds, ss, a);
     e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "d2d_step launch");
-    if (fresh_mode(h) && (e = fresh_regen(h, (hipStream_t)stream, false, h->cfg.auto_reset != 0)) !=
-                             hipSuccess)
+    if (fresh_mode(h) && (e = fresh_regen(h, ss, false, h->cfg.auto_reset != 0)) != hipSuccess)
         return hip_fail(e, "d2d_step: fresh scenarios");
     if (h->cfg.auto_reset && ++h->n_steps % FILL_PERIOD == 0) {
         // K4's cadence.  A step being captured into a graph launches K4 every FILL_PERIOD steps and
@@ -762,12 +619,11 @@ int32_t d2d_step(d2d_t* h, const float* act_dev, float* obs_dev, float* rew_dev,
         // says "skip" (~4 us each).  Either way an entry is an optimisation: a reset whose entry is
         // missing computes the same observation in K1.
         hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        if ((e = hipStreamIsCapturing((hipStream_t)stream, &cs)) != hipSuccess)
-            return hip_fail(e, "d2d_step: capture query");
+        if ((e = hipStreamIsCapturing(ss, &cs)) != hipSuccess) return hip_fail(e, "d2d_step: capture query");
         if (cs != hipStreamCaptureStatusNone) {
-            if ((e = rc_fill(h, (hipStream_t)stream)) != hipSuccess) return hip_fail(e, "d2d_step: cache fill");
+            if ((e = rc_fill(h, ss)) != hipSuccess) return hip_fail(e, "d2d_step: cache fill");
         } else if (h->n_steps % (FILL_PERIOD * FILL_EVERY) == 0) {
-            if ((e = rc_fill(h, (hipStream_t)stream, true)) != hipSuccess) return hip_fail(e, "d2d_step: cache fill");
+            if ((e = rc_fill(h, ss, true)) != hipSuccess) return hip_fail(e, "d2d_step: cache fill");
         }
     }
     return D2D_OK;
@@ -777,55 +633,23 @@ int32_t d2d_get_state(d2d_t* h, double* state_dev, int32_t* istate_dev, void* st
     if (!h) return fail(D2D_E_ARG, "d2d_get_state: null handle");
     DeviceGuard g(h->device);
     hipError_t e;
-    const size_t n = (size_t)h->n;
-    const hipStream_t s = (hipStream_t)stream;
-    if (h->lane_env) {  // grouped slot layout -> env order
-        if (state_dev && (e = permute(h->st, h->ns, h->env_slot, state_dev, h->n, (const int32_t*)nullptr, D2D_NSTATE,
-                                      h->n, s)) != hipSuccess)
-            return hip_fail(e, "d2d_get_state");
-        if (istate_dev && (e = permute(h->ist, h->ns, h->env_slot, istate_dev, h->n, (const int32_t*)nullptr,
-                                       D2D_NISTATE, h->n, s)) != hipSuccess)
-            return hip_fail(e, "d2d_get_state");
-        return D2D_OK;
-    }
-    if (state_dev &&
-        (e = hipMemcpyAsync(state_dev, h->st, sizeof(double) * D2D_NSTATE * n, hipMemcpyDeviceToDevice, s)) !=
-            hipSuccess)
-        return hip_fail(e, "d2d_get_state");
-    if (istate_dev &&
-        (e = hipMemcpyAsync(istate_dev, h->ist, sizeof(int32_t) * D2D_NISTATE * n, hipMemcpyDeviceToDevice, s)) !=
-            hipSuccess)
+    if ((e = copy_state<double>(h, true, h->lay.st.get(), state_dev, D2D_NSTATE, (hipStream_t)stream)) != hipSuccess ||
+        (e = copy_state<int32_t>(h, true, h->lay.ist.get(), istate_dev, D2D_NISTATE, (hipStream_t)stream)) != hipSuccess)
         return hip_fail(e, "d2d_get_state");
     return D2D_OK;
 }
 
 int32_t d2d_set_state(d2d_t* h, const double* state_dev, const int32_t* istate_dev, void* stream) {
     if (!h) return fail(D2D_E_ARG, "d2d_set_state: null handle");
-    if (h->n_scn <= 0) return fail(D2D_E_STATE, "d2d_set_state: call d2d_set_scenarios first");
+    if (h->tab.n_scn <= 0) return fail(D2D_E_STATE, "d2d_set_state: call d2d_set_scenarios first");
     DeviceGuard g(h->device);
     hipError_t e;
-    const size_t n = (size_t)h->n;
     const hipStream_t s = (hipStream_t)stream;
-    if (h->lane_env) {  // env order -> grouped slot layout
-        if (state_dev && (e = permute(state_dev, h->n, (const int32_t*)nullptr, h->st, h->ns, h->env_slot, D2D_NSTATE,
-                                      h->n, s)) != hipSuccess)
-            return hip_fail(e, "d2d_set_state");
-        if (istate_dev && (e = permute(istate_dev, h->n, (const int32_t*)nullptr, h->ist, h->ns, h->env_slot,
-                                       D2D_NISTATE, h->n, s)) != hipSuccess)
-            return hip_fail(e, "d2d_set_state");
-    } else {
-        if (state_dev &&
-            (e = hipMemcpyAsync(h->st, state_dev, sizeof(double) * D2D_NSTATE * n, hipMemcpyDeviceToDevice, s)) !=
-                hipSuccess)
-            return hip_fail(e, "d2d_set_state");
-        if (istate_dev &&
-            (e = hipMemcpyAsync(h->ist, istate_dev, sizeof(int32_t) * D2D_NISTATE * n, hipMemcpyDeviceToDevice, s)) !=
-                hipSuccess)
-            return hip_fail(e, "d2d_set_state");
-    }
-    if (fresh_mode(h) && (e = fresh_regen(h, (hipStream_t)stream)) != hipSuccess)
-        return hip_fail(e, "d2d_set_state: fresh scenarios");
-    if ((e = rc_rebuild(h, (hipStream_t)stream)) != hipSuccess) return hip_fail(e, "d2d_set_state: cache rebuild");
+    if ((e = copy_state<double>(h, false, state_dev, h->lay.st.get(), D2D_NSTATE, s)) != hipSuccess ||
+        (e = copy_state<int32_t>(h, false, istate_dev, h->lay.ist.get(), D2D_NISTATE, s)) != hipSuccess)
+        return hip_fail(e, "d2d_set_state");
+    if (fresh_mode(h) && (e = fresh_regen(h, s)) != hipSuccess) return hip_fail(e, "d2d_set_state: fresh scenarios");
+    if ((e = rc_rebuild(h, s)) != hipSuccess) return hip_fail(e, "d2d_set_state: cache rebuild");
     h->reset_done = true;
     return D2D_OK;
 }
@@ -833,15 +657,11 @@ int32_t d2d_set_state(d2d_t* h, const double* state_dev, const int32_t* istate_d
 int32_t d2d_refresh_pool(d2d_t* h, const d2d_scn* scns, int32_t n_scn) {
     if (!h || !scns) return fail(D2D_E_ARG, "d2d_refresh_pool: null handle/scenarios");
     if (h->cfg.scn_pool != 1) return fail(D2D_E_ARG, "d2d_refresh_pool: pool mode only (cfg.scn_pool = 1)");
-    if (h->n_scn <= 0) return fail(D2D_E_STATE, "d2d_refresh_pool: call d2d_set_scenarios first");
+    if (h->tab.n_scn <= 0) return fail(D2D_E_STATE, "d2d_refresh_pool: call d2d_set_scenarios first");
     if (n_scn != h->pool_n) return fail(D2D_E_ARG, "d2d_refresh_pool: n_scn must equal the pool size");
-    for (int k = 0; k < n_scn; ++k) {
-        const d2d_scn& s = scns[k];
-        if (s.n_wps < 3 || s.n_wps > D2D_MAX_WPS || s.n_circles < 0 || s.n_circles > D2D_MAX_CIRCLES)
-            return fail(D2D_E_ARG, "d2d_refresh_pool: invalid scenario");
-    }
     std::vector<unsigned char> tab;
-    if (!build_tables(h->rm, scns, (size_t)n_scn, tab)) return fail(D2D_E_ARG, "d2d_refresh_pool: invalid scenario");
+    if (scn_invalid(scns, (size_t)n_scn) || !build_tables(h->tab.rm, scns, (size_t)n_scn, tab))
+        return fail(D2D_E_ARG, "d2d_refresh_pool: invalid scenario");
     DeviceGuard g(h->device);
     hipError_t e;
     const size_t P = (size_t)n_scn;
@@ -850,21 +670,23 @@ int32_t d2d_refresh_pool(d2d_t* h, const d2d_scn* scns, int32_t n_scn) {
     // previous refresh): episodes last at most cfg.n_steps steps, so refreshes further apart are safe
     std::vector<int32_t> es((size_t)h->n);
     if ((e = hipDeviceSynchronize()) != hipSuccess ||  // in-flight steps may still draw from the old half
-        (e = hipMemcpy(es.data(), h->env_scn, sizeof(int32_t) * es.size(), hipMemcpyDeviceToHost)) != hipSuccess)
+        (e = hipMemcpy(es.data(), h->env_scn.get(), sizeof(int32_t) * es.size(), hipMemcpyDeviceToHost)) != hipSuccess)
         return hip_fail(e, "d2d_refresh_pool: read env_scn");
     int busy = 0;
     for (int32_t v : es) busy += (v >= half && v < half + n_scn);
     if (busy)
         return fail(D2D_E_STATE, "d2d_refresh_pool: " + std::to_string(busy) +
                                      " envs still run episodes from the pool before the previous refresh");
+    d2d_scn* abi = h->tab.abi.get();
+    d2d::BrTab* brt = h->tab.brt.get();
     if ((e = hipMemcpy(scn_at(h, half), tab.data(), tab.size(), hipMemcpyHostToDevice)) != hipSuccess ||
-        (h->abi && (e = hipMemcpy(h->abi + half, scns, P * sizeof(d2d_scn), hipMemcpyHostToDevice)) != hipSuccess) ||
-        (e = hipMemset(h->brt + half, 0, P * sizeof(d2d::BrTab))) != hipSuccess)
+        (abi && (e = hipMemcpy(abi + half, scns, P * sizeof(d2d_scn), hipMemcpyHostToDevice)) != hipSuccess) ||
+        (e = hipMemset(brt + half, 0, P * sizeof(d2d::BrTab))) != hipSuccess)
         return hip_fail(e, "d2d_refresh_pool: upload");
-    launch_brtab(h->rm, scn_at(h, half), n_scn, h->brt + half);
+    launch_brtab(h->tab.rm, scn_at(h, half), n_scn, brt + half);
     if ((e = hipGetLastError()) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess)
         return hip_fail(e, "d2d_refresh_pool: d2d_brtab_kernel");
-    if ((e = hipMemcpy(h->pool_dev, &half, sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess)
+    if ((e = hipMemcpy(h->pool_dev.get(), &half, sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess)
         return hip_fail(e, "d2d_refresh_pool: switch");
     h->pool_base = half;
     h->pool_valid |= (half == 0) ? 1 : 2;
@@ -878,7 +700,7 @@ int32_t d2d_refresh_pool(d2d_t* h, const d2d_scn* scns, int32_t n_scn) {
 int32_t d2d_get_env_scenarios(d2d_t* h, int32_t* env_scn_dev, void* stream) {
     if (!h || !env_scn_dev) return fail(D2D_E_ARG, "d2d_get_env_scenarios: null handle/out");
     DeviceGuard g(h->device);
-    hipError_t e = hipMemcpyAsync(env_scn_dev, h->env_scn, sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToDevice,
+    hipError_t e = hipMemcpyAsync(env_scn_dev, h->env_scn.get(), sizeof(int32_t) * (size_t)h->n, hipMemcpyDeviceToDevice,
                                   (hipStream_t)stream);
     if (e != hipSuccess) return hip_fail(e, "d2d_get_env_scenarios");
     return D2D_OK;
@@ -889,7 +711,7 @@ int32_t d2d_set_env_scenarios(d2d_t* h, const int32_t* env_scn_dev, void* stream
     if (h->cfg.scn_pool != 1)
         return fail(D2D_E_ARG, "d2d_set_env_scenarios: pool mode only (a static map changes with d2d_set_scenarios; "
                                "fresh curriculum slots are restored by d2d_fresh_recipes)");
-    if (h->n_scn <= 0) return fail(D2D_E_STATE, "d2d_set_env_scenarios: call d2d_set_scenarios first");
+    if (h->tab.n_scn <= 0) return fail(D2D_E_STATE, "d2d_set_env_scenarios: call d2d_set_scenarios first");
     DeviceGuard g(h->device);
     const hipStream_t s = (hipStream_t)stream;
     std::vector<int32_t> m((size_t)h->n);
@@ -897,11 +719,11 @@ int32_t d2d_set_env_scenarios(d2d_t* h, const int32_t* env_scn_dev, void* stream
     if (e == hipSuccess) e = hipStreamSynchronize(s);
     if (e != hipSuccess) return hip_fail(e, "d2d_set_env_scenarios: read map");
     for (int32_t v : m) {
-        if (v < 0 || v >= h->n_scn) return fail(D2D_E_ARG, "d2d_set_env_scenarios: scenario index out of range");
+        if (v < 0 || v >= h->tab.n_scn) return fail(D2D_E_ARG, "d2d_set_env_scenarios: scenario index out of range");
         if (!(h->pool_valid & (v >= h->pool_n ? 2 : 1)))
             return fail(D2D_E_ARG, "d2d_set_env_scenarios: index into a pool half that holds no scenarios");
     }
-    if ((e = hipMemcpyAsync(h->env_scn, m.data(), sizeof(int32_t) * m.size(), hipMemcpyHostToDevice, s)) != hipSuccess ||
+    if ((e = hipMemcpyAsync(h->env_scn.get(), m.data(), sizeof(int32_t) * m.size(), hipMemcpyHostToDevice, s)) != hipSuccess ||
         (e = hipStreamSynchronize(s)) != hipSuccess)
         return hip_fail(e, "d2d_set_env_scenarios");
     return D2D_OK;
@@ -909,7 +731,7 @@ int32_t d2d_set_env_scenarios(d2d_t* h, const int32_t* env_scn_dev, void* stream
 
 int32_t d2d_pool_state(d2d_t* h, int32_t* active_base, int32_t* valid_mask) {
     if (!h || !active_base || !valid_mask) return fail(D2D_E_ARG, "d2d_pool_state: null argument");
-    if (h->cfg.scn_pool != 1 || h->n_scn <= 0) return fail(D2D_E_STATE, "d2d_pool_state: pool mode with scenarios only");
+    if (h->cfg.scn_pool != 1 || h->tab.n_scn <= 0) return fail(D2D_E_STATE, "d2d_pool_state: pool mode with scenarios only");
     *active_base = h->pool_base;
     *valid_mask = h->pool_valid;
     return D2D_OK;
@@ -917,23 +739,20 @@ int32_t d2d_pool_state(d2d_t* h, int32_t* active_base, int32_t* valid_mask) {
 
 int32_t d2d_restore_pool(d2d_t* h, const d2d_scn* scns, int32_t n_total, int32_t active_base, int32_t valid_mask) {
     if (!h || !scns) return fail(D2D_E_ARG, "d2d_restore_pool: null argument");
-    if (h->cfg.scn_pool != 1 || h->n_scn <= 0) return fail(D2D_E_STATE, "d2d_restore_pool: pool mode with scenarios only");
+    if (h->cfg.scn_pool != 1 || h->tab.n_scn <= 0) return fail(D2D_E_STATE, "d2d_restore_pool: pool mode with scenarios only");
     const int P = h->pool_n;
     if (n_total != 2 * P) return fail(D2D_E_ARG, "d2d_restore_pool: n_total must be twice the pool size");
     if (active_base != 0 && active_base != P) return fail(D2D_E_ARG, "d2d_restore_pool: active_base must be 0 or pool_n");
     if (!(valid_mask & (active_base ? 2 : 1)) || (valid_mask & ~3))
         return fail(D2D_E_ARG, "d2d_restore_pool: the active half must be valid");
     std::vector<bool> use((size_t)n_total);
-    for (int k = 0; k < n_total; ++k) {
-        use[k] = (valid_mask & (k >= P ? 2 : 1)) != 0;
-        if (!use[k]) continue;
-        const d2d_scn& sc = scns[k];
-        if (sc.n_wps < 3 || sc.n_wps > D2D_MAX_WPS || sc.n_circles < 0 || sc.n_circles > D2D_MAX_CIRCLES)
-            return fail(D2D_E_ARG, "d2d_restore_pool: invalid scenario");
-    }
+    for (int k = 0; k < n_total; ++k) use[(size_t)k] = (valid_mask & (k >= P ? 2 : 1)) != 0;
     std::vector<unsigned char> tab;
-    if (!build_tables(h->rm, scns, (size_t)n_total, tab, &use)) return fail(D2D_E_ARG, "d2d_restore_pool: invalid scenario");
-    const size_t sz = scn_size(h->rm);
+    if (scn_invalid(scns, (size_t)n_total, &use) || !build_tables(h->tab.rm, scns, (size_t)n_total, tab, &use))
+        return fail(D2D_E_ARG, "d2d_restore_pool: invalid scenario");
+    const size_t sz = scn_size(h->tab.rm);
+    d2d_scn* abi = h->tab.abi.get();
+    d2d::BrTab* brt = h->tab.brt.get();
     DeviceGuard g(h->device);
     hipError_t e;
     if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail(e, "d2d_restore_pool: sync");
@@ -941,19 +760,19 @@ int32_t d2d_restore_pool(d2d_t* h, const d2d_scn* scns, int32_t n_total, int32_t
         const size_t o = (size_t)half * P;
         if (!(valid_mask & (1 << half))) {
             if ((e = hipMemset(scn_at(h, o), 0, P * sz)) != hipSuccess ||
-                (e = hipMemset(h->abi + o, 0, P * sizeof(d2d_scn))) != hipSuccess ||
-                (e = hipMemset(h->brt + o, 0, P * sizeof(d2d::BrTab))) != hipSuccess)
+                (e = hipMemset(abi + o, 0, P * sizeof(d2d_scn))) != hipSuccess ||
+                (e = hipMemset(brt + o, 0, P * sizeof(d2d::BrTab))) != hipSuccess)
                 return hip_fail(e, "d2d_restore_pool: clear");
             continue;
         }
         if ((e = hipMemcpy(scn_at(h, o), tab.data() + o * sz, P * sz, hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemcpy(h->abi + o, scns + o, P * sizeof(d2d_scn), hipMemcpyHostToDevice)) != hipSuccess ||
-            (e = hipMemset(h->brt + o, 0, P * sizeof(d2d::BrTab))) != hipSuccess)
+            (e = hipMemcpy(abi + o, scns + o, P * sizeof(d2d_scn), hipMemcpyHostToDevice)) != hipSuccess ||
+            (e = hipMemset(brt + o, 0, P * sizeof(d2d::BrTab))) != hipSuccess)
             return hip_fail(e, "d2d_restore_pool: upload");
-        launch_brtab(h->rm, scn_at(h, o), P, h->brt + o);
+        launch_brtab(h->tab.rm, scn_at(h, o), P, brt + o);
         if ((e = hipGetLastError()) != hipSuccess) return hip_fail(e, "d2d_restore_pool: d2d_brtab_kernel");
     }
-    if ((e = hipMemcpy(h->pool_dev, &active_base, sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess ||
+    if ((e = hipMemcpy(h->pool_dev.get(), &active_base, sizeof(int32_t), hipMemcpyHostToDevice)) != hipSuccess ||
         (e = hipDeviceSynchronize()) != hipSuccess)
         return hip_fail(e, "d2d_restore_pool: switch");
     h->pool_base = active_base;
@@ -974,66 +793,61 @@ int32_t d2d_set_curriculum(d2d_t* h, const d2d_curriculum* c) {
     DeviceGuard g(h->device);
     hipError_t e;
     const size_t S = 2 * (size_t)h->n;
-    if (h->n_scn != (int)S || !h->scn_tag) {
+    // the first curriculum of a handle builds its tables and slots, later ones keep them; the handle
+    // takes them only once all of them exist
+    const bool build = h->tab.n_scn != (int)S || !h->fresh.scn_tag;
+    ScnTables tab;
+    FreshSlots fr;
+    if (build) {
+        tab.n_scn = (int)S;
+        tab.rm = place(true, false, S, false).rm;  // (read per lane from global memory; no golden-march tables)
+        fr.ring = ring_size(S);
         if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail(e, "d2d_set_curriculum: sync");
-        for (void* p : {(void*)h->scn, (void*)h->brt, (void*)h->abi, (void*)h->scn_tag, (void*)h->gclk,
-                        (void*)h->fresh_q})  // (fresh mode keeps no golden-march tables: brt stays null)
-            if (p) (void)hipFree(p);
-        h->scn = nullptr;
-        h->brt = nullptr;
-        h->abi = nullptr;
-        h->scn_tag = nullptr;
-        h->gclk = nullptr;
-        h->fresh_q = nullptr;
-        h->fresh_ring = ring_size(S);
-        h->n_scn = 0;
-        h->rm = true;  // (the fresh curriculum's tables are read per lane from global memory)
-        if ((e = hipMalloc(&h->scn, sizeof(d2d::ScnR) * S)) != hipSuccess ||
-            (e = hipMalloc(&h->abi, sizeof(d2d_scn) * S)) != hipSuccess ||
-            (e = hipMalloc(&h->scn_tag, sizeof(int32_t) * S)) != hipSuccess ||
-            (e = hipMalloc(&h->gclk, sizeof(int64_t) * S)) != hipSuccess ||
-            (e = hipMalloc(&h->fresh_q, sizeof(int32_t) * (ring_size(S) + FR_WORDS))) != hipSuccess ||
-            (e = hipMemset(h->fresh_q, 0, sizeof(int32_t) * (ring_size(S) + FR_WORDS))) != hipSuccess ||
-            (e = hipMemset(h->scn, 0, sizeof(d2d::ScnR) * S)) != hipSuccess ||
-            (e = hipMemset(h->abi, 0, sizeof(d2d_scn) * S)) != hipSuccess ||
-            (e = hipMemset(h->gclk, 0, sizeof(int64_t) * S)) != hipSuccess)
+        if ((e = dev_new(tab.scn, scn_size(tab.rm) * S)) != hipSuccess || (e = dev_new(tab.abi, S)) != hipSuccess ||
+            (e = dev_new(fr.scn_tag, S)) != hipSuccess || (e = dev_new(fr.gclk, S)) != hipSuccess ||
+            (e = dev_new(fr.queue, fr.ring + FR_WORDS)) != hipSuccess)
             return hip_fail(e, "d2d_set_curriculum: hipMalloc");
     }
+    const FreshSlots& f = build ? fr : h->fresh;
     // the schedule restarts at c->sim_num0: sim_num = sim_num0 + clock * envs_total counts the steps
     // taken on THIS curriculum, not those since the handle was created
-    if ((e = hipMemset(h->scn_tag, 0xFF, sizeof(int32_t) * S)) != hipSuccess ||
-        (e = hipMemset(h->clock, 0, sizeof(int64_t))) != hipSuccess ||
-        (e = hipMemset(h->fresh_q + h->fresh_ring, 0, sizeof(int32_t) * FR_WORDS)) != hipSuccess ||  // (FreshRing)
+    if ((e = hipMemset(f.scn_tag.get(), 0xFF, sizeof(int32_t) * S)) != hipSuccess ||
+        (e = hipMemset(h->clock.get(), 0, sizeof(int64_t))) != hipSuccess ||
+        (e = hipMemset(f.words(), 0, sizeof(int32_t) * FR_WORDS)) != hipSuccess ||  // (FreshRing)
         (e = hipDeviceSynchronize()) != hipSuccess)
         return hip_fail(e, "d2d_set_curriculum: slots");
+    if (build) {
+        h->tab = std::move(tab);
+        h->fresh = std::move(fr);
+    }
     h->cur = *c;
-    h->n_scn = (int)S;
     h->pool_n = 0;
     h->fresh_seeded = false;
     h->reset_done = false;  // every env starts over on the new curriculum (d2d_reset)
-    h->rc_dirty = true;
-    h->generation += 1;
+    h->stale();
     return D2D_OK;
 }
 
 int32_t d2d_fresh_recipes(d2d_t* h, int32_t* keys, int64_t* clocks, int64_t* clock, int32_t set) {
     if (!h || !keys || !clocks || !clock) return fail(D2D_E_ARG, "d2d_fresh_recipes: null argument");
-    if (!fresh_mode(h) || !h->scn_tag) return fail(D2D_E_STATE, "d2d_fresh_recipes: call d2d_set_curriculum first");
+    if (!fresh_mode(h) || !h->fresh.scn_tag) return fail(D2D_E_STATE, "d2d_fresh_recipes: call d2d_set_curriculum first");
     DeviceGuard g(h->device);
     hipError_t e;
     const size_t S = 2 * (size_t)h->n;
+    int32_t* tag = h->fresh.scn_tag.get();
+    int64_t* gclk = h->fresh.gclk.get();
     if ((e = hipDeviceSynchronize()) != hipSuccess) return hip_fail(e, "d2d_fresh_recipes: sync");
     if (!set) {
-        if ((e = hipMemcpy(keys, h->scn_tag, sizeof(int32_t) * S, hipMemcpyDeviceToHost)) != hipSuccess ||
-            (e = hipMemcpy(clocks, h->gclk, sizeof(int64_t) * S, hipMemcpyDeviceToHost)) != hipSuccess ||
-            (e = hipMemcpy(clock, h->clock, sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess)
+        if ((e = hipMemcpy(keys, tag, sizeof(int32_t) * S, hipMemcpyDeviceToHost)) != hipSuccess ||
+            (e = hipMemcpy(clocks, gclk, sizeof(int64_t) * S, hipMemcpyDeviceToHost)) != hipSuccess ||
+            (e = hipMemcpy(clock, h->clock.get(), sizeof(int64_t), hipMemcpyDeviceToHost)) != hipSuccess)
             return hip_fail(e, "d2d_fresh_recipes: read");
         return D2D_OK;
     }
     if (!h->fresh_seeded) return fail(D2D_E_STATE, "d2d_fresh_recipes: call d2d_reset (the seed) before restoring");
-    if ((e = hipMemcpy(h->scn_tag, keys, sizeof(int32_t) * S, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(h->gclk, clocks, sizeof(int64_t) * S, hipMemcpyHostToDevice)) != hipSuccess ||
-        (e = hipMemcpy(h->clock, clock, sizeof(int64_t), hipMemcpyHostToDevice)) != hipSuccess)
+    if ((e = hipMemcpy(tag, keys, sizeof(int32_t) * S, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(gclk, clocks, sizeof(int64_t) * S, hipMemcpyHostToDevice)) != hipSuccess ||
+        (e = hipMemcpy(h->clock.get(), clock, sizeof(int64_t), hipMemcpyHostToDevice)) != hipSuccess)
         return hip_fail(e, "d2d_fresh_recipes: write");
     if ((e = fresh_regen(h, nullptr, true)) != hipSuccess || (e = hipDeviceSynchronize()) != hipSuccess)
         return hip_fail(e, "d2d_fresh_recipes: regenerate");
@@ -1043,12 +857,12 @@ int32_t d2d_fresh_recipes(d2d_t* h, int32_t* keys, int64_t* clocks, int64_t* clo
 
 int32_t d2d_get_scenario_table(d2d_t* h, int32_t first, int32_t count, d2d_scn* out) {
     if (!h || !out || first < 0 || count < 0) return fail(D2D_E_ARG, "d2d_get_scenario_table: bad arguments");
-    if (!h->abi) return fail(D2D_E_STATE, "d2d_get_scenario_table: pool or fresh curriculum mode with scenarios only");
-    if (first + count > h->n_scn) return fail(D2D_E_ARG, "d2d_get_scenario_table: range beyond the table");
+    if (!h->tab.abi) return fail(D2D_E_STATE, "d2d_get_scenario_table: pool or fresh curriculum mode with scenarios only");
+    if (first + count > h->tab.n_scn) return fail(D2D_E_ARG, "d2d_get_scenario_table: range beyond the table");
     DeviceGuard g(h->device);
     hipError_t e;
     if ((e = hipDeviceSynchronize()) != hipSuccess ||
-        (e = hipMemcpy(out, h->abi + first, sizeof(d2d_scn) * (size_t)count, hipMemcpyDeviceToHost)) != hipSuccess)
+        (e = hipMemcpy(out, h->tab.abi.get() + first, sizeof(d2d_scn) * (size_t)count, hipMemcpyDeviceToHost)) != hipSuccess)
         return hip_fail(e, "d2d_get_scenario_table");
     return D2D_OK;
 }
@@ -1058,8 +872,9 @@ int32_t d2d_generation(const d2d_t* h) { return h ? h->generation : -1; }
 int32_t d2d_episode_stats(d2d_t* h, double* out_dev, int32_t clear, void* stream) {
     if (!h || !out_dev) return fail(D2D_E_ARG, "d2d_episode_stats: null handle/out");
     DeviceGuard g(h->device);
-    hipLaunchKernelGGL(d2d_stats_kernel, dim3(D2D_NSTATS), dim3(BLOCK), 0, (hipStream_t)stream, h->acc, h->ns,
-                       out_dev, clear, h->acc);
+    double* acc = h->lay.acc.get();
+    hipLaunchKernelGGL(d2d_stats_kernel, dim3(D2D_NSTATS), dim3(BLOCK), 0, (hipStream_t)stream, acc, h->lay.ns, out_dev,
+                       clear, acc);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return hip_fail(e, "d2d_episode_stats launch");
     return D2D_OK;
@@ -1068,42 +883,25 @@ int32_t d2d_episode_stats(d2d_t* h, double* out_dev, int32_t clear, void* stream
 int32_t d2d_group_layout(int32_t n, const int32_t* env_scn, int32_t n_scn, int32_t* slot_env, int32_t* group_scn) {
     if (n <= 0 || n_scn <= 0 || !env_scn || !slot_env || !group_scn)
         return fail(D2D_E_ARG, "d2d_group_layout: n, n_scn must be > 0 and pointers non-null"), -1;
-    for (int i = 0; i < n; ++i)
-        if (env_scn[i] < 0 || env_scn[i] >= n_scn)
-            return fail(D2D_E_ARG, "d2d_group_layout: env scenario index out of range"), -1;
-    std::vector<int32_t> lanes, ws;
-    make_groups(n, env_scn, n_scn, lanes, ws);
-    std::copy(lanes.begin(), lanes.end(), slot_env);
-    std::copy(ws.begin(), ws.end(), group_scn);
-    return (int32_t)ws.size();
+    return group_layout("d2d_group_layout", n, env_scn, n_scn, nullptr, 0, slot_env, group_scn);
 }
 
 int32_t d2d_balanced_group_layout(int32_t n, const int32_t* env_scn, int32_t n_scn, const double* cost, int32_t n_cu,
                                   int32_t* slot_env, int32_t* group_scn) {
     if (n <= 0 || n_scn <= 0 || !env_scn || !cost || !slot_env || !group_scn || n_cu < 0)
         return fail(D2D_E_ARG, "d2d_balanced_group_layout: bad arguments"), -1;
-    for (int i = 0; i < n; ++i)
-        if (env_scn[i] < 0 || env_scn[i] >= n_scn)
-            return fail(D2D_E_ARG, "d2d_balanced_group_layout: env scenario index out of range"), -1;
-    std::vector<int32_t> lanes, ws;
-    make_groups(n, env_scn, n_scn, lanes, ws);
-    balance_groups(n_cu, cost, n_scn, lanes, ws);
-    std::copy(lanes.begin(), lanes.end(), slot_env);
-    std::copy(ws.begin(), ws.end(), group_scn);
-    return (int32_t)ws.size();
+    return group_layout("d2d_balanced_group_layout", n, env_scn, n_scn, cost, n_cu, slot_env, group_scn);
 }
 
 int32_t d2d_selftest(int32_t which, int64_t n, uint64_t seed, uint64_t* mismatches) {
     if (!mismatches || n < 0 || which < 0 || which > 2) return fail(D2D_E_ARG, "d2d_selftest: bad arguments");
-    unsigned long long* bad = nullptr;
+    DevBuf<unsigned long long> bad;
     hipError_t e;
-    if ((e = hipMalloc(&bad, sizeof(unsigned long long))) != hipSuccess) return hip_fail(e, "d2d_selftest alloc");
-    (void)hipMemset(bad, 0, sizeof(unsigned long long));
-    hipLaunchKernelGGL(d2d_selftest_kernel, dim3(2048), dim3(256), 0, 0, which, (long long)n, seed, bad);
+    if ((e = dev_new(bad, 1)) != hipSuccess) return hip_fail(e, "d2d_selftest alloc");
+    hipLaunchKernelGGL(d2d_selftest_kernel, dim3(2048), dim3(256), 0, 0, which, (long long)n, seed, bad.get());
     e = hipGetLastError();
     unsigned long long h = 0;
-    if (e == hipSuccess) e = hipMemcpy(&h, bad, sizeof(h), hipMemcpyDeviceToHost);
-    (void)hipFree(bad);
+    if (e == hipSuccess) e = hipMemcpy(&h, bad.get(), sizeof(h), hipMemcpyDeviceToHost);
     if (e != hipSuccess) return hip_fail(e, "d2d_selftest");
     *mismatches = (uint64_t)h;
     return D2D_OK;

@@ -1,4 +1,5 @@
-// d2d_kernels.h -- the kernels of libdrone2d_hip.so (included by d2d_hip.hip).
+// d2d_kernels.h -- the kernels of libdrone2d_hip.so (included by d2d_hip.hip; includes d2d_device.h,
+// d2d_curriculum.h and d2d_layout.h, the host's slot-layout code with the shared xcd_group).
 //
 // K1 d2d_step_kernel (cooperative, wave-specialised).  One 256-lane workgroup owns 64 envs (one
 // per lane index); its four waves split one env step by role so that the long, independent fp64
@@ -33,12 +34,12 @@
 
 #include "d2d_curriculum.h"
 #include "d2d_device.h"
+#include "d2d_layout.h"
 
 namespace d2dk {
 using namespace d2d;
 
 constexpr int BLOCK = 256;      // K2 / K3 workgroup
-constexpr int EPB = 64;         // K1: envs per workgroup
 constexpr int K1_THREADS = 256; // K1: 4 waves
 // scenario tables go to LDS when they fit next to K1's own LDS within the 4-workgroups-per-CU
 // budget (160 KB / 4); larger sets are read from global memory (L1/L2 resident)
@@ -109,7 +110,7 @@ struct StepArgs {
 };
 
 // the scenario table in the layout the launch was instantiated for (ScnF: the handle stages its
-// scenarios in LDS; ScnR: K1 reads them from global memory, d2d_hip.hip table_rm)
+// scenarios in LDS; ScnR: K1 reads them from global memory, d2d_hip.hip place)
 template <class S>
 __device__ __forceinline__ const S* scn_tab(const StepArgs& a) { return static_cast<const S*>(a.scn); }
 
@@ -207,16 +208,6 @@ __device__ __forceinline__ void glds_copy(void* lds_dst, const void* gsrc, int b
         if (off < bytes)
             __builtin_amdgcn_global_load_lds((GP*)((const char*)gsrc + off), (LP*)((char*)lds_dst + c * 1024), 16, 0, 0);
     }
-}
-
-// Workgroup renumbering for the grouped lane map: blocks b and b + 8 share an XCD (and its L2)
-// when the grid is dealt round-robin over the 8 XCDs, so consecutive group numbers -- groups whose
-// envs share cache lines -- go to blocks on one XCD.  Placement only affects speed.
-// XCD x = b % 8 holds per + (x < rem) blocks; its k-th block (k = b / 8) takes group number
-// (groups of XCDs before x) + k, a bijection on [0, nb).
-__device__ __forceinline__ int xcd_group(int b, int nb) {
-    const int per = nb / 8, rem = nb % 8, x = b % 8, k = b / 8;
-    return (x < rem) ? x * (per + 1) + k : rem * (per + 1) + (x - rem) * per + k;
 }
 
 __device__ __forceinline__ size_t fidx(int f, int n, int i) { return (size_t)f * (size_t)n + (size_t)i; }

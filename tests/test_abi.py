@@ -214,6 +214,23 @@ def test_balanced_group_layout(hip_lib, n, n_cu):
         assert len(strad) == len(set(strad))
 
 
+def test_layout_host_code_sanitized(tmp_path):
+    """csrc/d2d_layout.h (make_groups, balance_groups, xcd_group: the host code behind the two tests
+    above) as a stand-alone program under the address and undefined-behaviour sanitizers:
+    tests/layout_host_main.cpp runs those tests' maps and (n, n_cu) pairs and the edges (n = 1, 63,
+    64, 65, a scenario without envs, n_cu = 0 / 8 / not a multiple of 8, more groups than 4 n_cu, a
+    cost table shorter than the scenario count) and checks that env <-> slot is a bijection and
+    that balancing only permutes groups."""
+    from drone2d_amd import _build
+
+    exe = tmp_path / "layout_host"
+    subprocess.run(["g++", "-std=c++17", "-O1", "-g", "-fsanitize=address,undefined", "-fno-sanitize-recover=all",
+                    "-I", os.path.join(_build.PKG_DIR, "csrc"), os.path.join(REPO, "tests", "layout_host_main.cpp"),
+                    "-o", str(exe)], check=True)
+    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+
+
 def test_philox_known_answers(oracle_mod):
     """Random123 Philox4x32-10 KAT vectors (the spawn RNG spec shared by kernel and oracle)."""
     assert oracle_mod.philox([0, 0, 0, 0], [0, 0]) == [0x6627E8D5, 0xE169C58D, 0xBC57AC4C, 0x9B00DBD8]

@@ -119,12 +119,17 @@ def test_grouped_lane_map_irregular(d2):
     venv.close()
 
 
-def test_layout_change_keeps_state(d2):
+@pytest.mark.parametrize("n", [777, 4096])
+def test_layout_change_keeps_state(d2, n):
     """d2d_set_scenarios with a new env -> scenario map moves the running state into the new slot
     layout (grouped -> regrouped -> identity): get_state in env order and the episode statistics are
-    unchanged, and stepping continues in parity with the oracle."""
+    unchanged, and stepping continues in parity with the oracle.  So does d2d_set_scenario_costs with
+    the costs reversed on the live batch: it renumbers the groups inside each XCD chunk (at 777 envs,
+    13 groups, a chunk holds one or two groups and the renumbering may be the identity; at 4 096
+    envs, 64 groups, it is not)."""
+    import ctypes as C
+
     rng = np.random.default_rng(9)
-    n = 777
     es = rng.integers(0, 7, n).astype(np.int32)
     venv, orc = make_pair(d2, n, SCENARIOS, seed=4, kwargs=_cfgkw(), env_scenario=es)
     for _ in range(40):
@@ -137,7 +142,22 @@ def test_layout_change_keeps_state(d2):
         np.testing.assert_array_equal(st1, st0)
         np.testing.assert_array_equal(ist1, ist0)
         np.testing.assert_allclose(venv.episode_stats(clear=False).cpu().numpy(), stats0, rtol=1e-12)
-    # back on the original map: keeps stepping in parity (the reset cache was dropped and refilled)
+    # back on the original map (grouped, balanced by the scenarios' step costs): reversed costs
+    from drone2d_amd.config import SCENARIO_STEP_COST
+
+    lay0 = venv.group_layout()
+    cost = [SCENARIO_STEP_COST[s] for s in SCENARIOS][::-1]
+    venv._check(venv._lib.d2d_set_scenario_costs(venv._h, (C.c_double * len(cost))(*cost), len(cost)),
+                "d2d_set_scenario_costs")
+    st1, ist1 = (x.cpu().numpy() for x in venv.get_state())
+    np.testing.assert_array_equal(st1, st0)
+    np.testing.assert_array_equal(ist1, ist0)
+    np.testing.assert_allclose(venv.episode_stats(clear=False).cpu().numpy(), stats0, rtol=1e-12)
+    lay1 = venv.group_layout()
+    assert sorted(lay1[0][lay1[0] >= 0].tolist()) == list(range(n))
+    if n == 4096:
+        assert not np.array_equal(lay1[0], lay0[0])
+    # keeps stepping in parity (the reset cache was dropped and refilled)
     for _ in range(30):
         compare_step(venv, orc, np.clip(rng.normal(0.0, 0.6, (n, 2)), -1, 1).astype(np.float32))
     venv.close()
