@@ -26,6 +26,12 @@ EXACT_OUT = os.path.join(PKG_DIR, "_lib", "libdrone2d_hip_exact.so")
 PPO_SRC = os.path.join(PKG_DIR, "csrc", "d2d_ppo.hip")
 PPO_HDRS = [os.path.join(REPO, "include", "d2d_ppo.h")]
 PPO_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_ppo.so")
+# the renderer (include/d2d_render.h): a library of its own, under csrc/render/ so that env_headers()'
+# glob of csrc/*.h does not make the env library rebuild with it
+RENDER_SRC = os.path.join(PKG_DIR, "csrc", "render", "d2d_render.hip")
+RENDER_HDRS = [os.path.join(PKG_DIR, "csrc", "render", "d2d_raster.h"), os.path.join(PKG_DIR, "csrc", "d2d_pmath.h"),
+               os.path.join(REPO, "include", "d2d_render.h"), os.path.join(REPO, "include", "drone2d.h")]
+RENDER_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_render.so")
 
 # -ffp-contract=off: the kernels follow the reference's NumPy evaluation order (explicit fma() only
 # where NumPy/OpenBLAS fuses); no fast-math: IEEE inf/NaN semantics are part of the contract.
@@ -73,9 +79,19 @@ def build_exact(force: bool = False, verbose: bool = False) -> str:
     return EXACT_OUT
 
 
+def build_render(force: bool = False, verbose: bool = False) -> str:
+    """The renderer (libd2d_render.so), with the env's flags: -ffp-contract=off is what makes its host
+    twins and its kernels round alike.  Compiled by ``build()`` or by the first ``render()`` that
+    finds it missing."""
+    if force or needs_build(RENDER_OUT, RENDER_SRC, RENDER_HDRS):
+        _compile(RENDER_SRC, RENDER_OUT, verbose)
+    return RENDER_OUT
+
+
 def build(force: bool = False, verbose: bool = False, exact: bool = False) -> str:
     """The in-tree libraries: the env (libdrone2d_hip.so: every mode, one scenario layout), the PPO
-    update kernels (libd2d_ppo.so) and, with ``exact``, the env's exact-trig build."""
+    update kernels (libd2d_ppo.so), the renderer (libd2d_render.so) and, with ``exact``, the env's
+    exact-trig build."""
     stale = os.path.join(PKG_DIR, "_lib", "libdrone2d_hip_rm.so")  # rounds 1-3's second layout build
     if os.path.exists(stale):
         os.remove(stale)
@@ -85,4 +101,5 @@ def build(force: bool = False, verbose: bool = False, exact: bool = False) -> st
         build_exact(force, verbose)
     if force or needs_build(PPO_OUT, PPO_SRC, PPO_HDRS):
         _compile(PPO_SRC, PPO_OUT, verbose, PPO_FLAGS)
+    build_render(force, verbose)
     return OUT

@@ -205,6 +205,7 @@ class Drone2dVecEnv:
         check(code, what, self._lib)  # the error text of this handle's library
 
     def _upload_scenarios(self, env_scenario=None):
+        self._render_table = None  # render()'s device copy of the static scenario table
         if self.fresh:
             self.curriculum = make_curriculum(self.kwargs, self.envs_total)
             self.env_scenario = 2 * np.arange(self.num_envs, dtype=np.int32)
@@ -291,6 +292,10 @@ class Drone2dVecEnv:
         return C.c_void_p(t.data_ptr()) if t is not None else None
 
     def close(self):
+        r = getattr(self, "_renderer", None)
+        if r is not None:
+            r.close()
+            self._renderer = None
         if getattr(self, "_h", None):
             torch.cuda.synchronize(self.device)
             self._lib.d2d_destroy(self._h)
@@ -456,6 +461,79 @@ class Drone2dVecEnv:
             raise ValueError("checkpoint env -> scenario map differs from this batch's (static map)")
         self.set_state(sd["state"], sd["istate"])
 
+    # ------------------------------------------------------------------ rendering
+    def _render_ids(self, env_ids) -> torch.Tensor:
+        if env_ids is None:
+            env_ids = range(min(self.num_envs, 16))
+        ids = torch.as_tensor(list(env_ids) if not isinstance(env_ids, (torch.Tensor, np.ndarray)) else env_ids)
+        ids = ids.to(torch.int64).reshape(-1).cpu()
+        if len(ids) and (int(ids.min()) < 0 or int(ids.max()) >= self.num_envs):
+            raise ValueError("env_ids out of range")
+        return ids
+
+    def render_scenarios(self, env_ids=None, istate: torch.Tensor | None = None):
+        """The ABI record (abi.D2DScn array) of the scenario each of ``env_ids`` is running now -- what
+        ``render`` draws: the static map's entry; in curriculum pool mode the table slot
+        ``get_env_scenarios`` names; in the fresh curriculum the slot of the running episode,
+        2 i + ((episode - 1) & 1) (csrc/d2d_kernels.h fresh_slot)."""
+        ids = self._render_ids(env_ids).numpy()
+        if not self.cfg.scn_pool:
+            return (abi.D2DScn * len(ids))(*[self.scenarios[int(self.env_scenario[i])].to_c() for i in ids])
+        if self.fresh:
+            ist = self.get_state()[1] if istate is None else istate
+            ep = ist[abi.I_EPISODE].cpu().numpy()[ids]
+            slots = 2 * ids + ((ep - 1) & 1)
+        else:
+            slots = self.get_env_scenarios().cpu().numpy()[ids]
+        if not len(slots):
+            return (abi.D2DScn * 0)()
+        lo, hi = int(slots.min()), int(slots.max())
+        table = self.scenario_table(lo, hi - lo + 1)
+        return (abi.D2DScn * len(ids))(*[table[int(k) - lo] for k in slots])
+
+    def render(self, env_ids=None, size=256, layers: int | None = None, trails=None) -> torch.Tensor:
+        """Frames of the envs ``env_ids`` (default: the first min(num_envs, 16)) as they are now:
+        uint8 [K, H, W, 3] on the env's device, drawn by libd2d_render.so (drone2d_amd.render has the
+        picture model).  ``size``: an int or (H, W); ``layers``: a mask of render.L_* (default all);
+        ``trails``: (xy float32 [K, T, 2] world positions, length int32 [K]) or None.  Each frame shows
+        the env's running scenario, its state, its current observation's closest and lookahead points
+        and the last action's forces.  The renderer and its library are created on first use."""
+        from . import render as R
+
+        ids = self._render_ids(env_ids)
+        k = len(ids)
+        h, w = R._size(size)
+        if k == 0:
+            return torch.empty((0, h, w, 3), dtype=torch.uint8, device=self.device)
+        tr = tl = None
+        if trails is not None:
+            tr, tl = trails
+            tr = torch.as_tensor(tr, dtype=torch.float32)
+            tl = torch.as_tensor(tl, dtype=torch.int32)
+            if tr.dim() != 3 or tuple(tr.shape[::2]) != (k, 2) or tuple(tl.shape) != (k,):
+                raise ValueError("trails must be (xy [K, T, 2], length [K])")
+        need_trail = int(tr.shape[1]) if tr is not None else 0
+        r = getattr(self, "_renderer", None)
+        if r is None or r.max_frames < k or r.max_trail < need_trail:
+            caps = (max(k, 16, r.max_frames if r else 0), max(need_trail, r.max_trail if r else 0))
+            if r is not None:
+                r.close()
+            r = self._renderer = R.Renderer(self.device, max_frames=caps[0], max_trail=caps[1])
+        if tr is not None and tr.shape[1] < r.max_trail:  # the library's trail rows are max_trail long
+            tr = torch.cat([tr, tr.new_zeros(k, r.max_trail - tr.shape[1], 2)], 1)
+        st, ist = self.get_state()
+        dids = ids.to(self.device)
+        if not self.cfg.scn_pool:
+            if self._render_table is None:
+                self._render_table = r.scn_tensor(self.scenarios)
+            scn = self._render_table[torch.as_tensor(self.env_scenario, dtype=torch.int64)[ids].to(self.device)]
+        else:
+            scn = r.scn_tensor(self.render_scenarios(ids, ist))
+        act = getattr(self, "_last_actions", None)
+        return r.render(scn, st[:, dids], self._bufs[self._k]["obs"][dids], act[dids] if act is not None else None,
+                        tr, tl, size=(h, w), screen=(self.cfg.screen_w, self.cfg.screen_h),
+                        layers=R.L_ALL if layers is None else int(layers))
+
     def episode_stats(self, clear: bool = True) -> torch.Tensor:
         """float64 [8]: (sum return, episodes, successes, fails, collisions, sum APE, sum len, 0)."""
         self._check(self._lib.d2d_episode_stats(self._h, self._ptr(self._stats), 1 if clear else 0, self._stream()),
@@ -507,10 +585,12 @@ class Drone2dEnv:
 
     Differences, all deliberate: observations are float32 values returned as a float64 array
     (the reference builds float64 from the same expressions); the spawn draw comes from the
-    library's Philox stream instead of Python's unseeded ``random``; render keys are ignored.
+    library's Philox stream instead of Python's unseeded ``random``; ``render`` draws
+    ``rgb_array`` frames with the project's own picture model (drone2d_amd.render) and opens no
+    window (``render_sim`` / ``render_shade`` / ``render_text`` are ignored).
     """
 
-    metadata = {"render.modes": []}
+    metadata = {"render.modes": ["rgb_array"]}
 
     def __init__(self, **kwargs):
         self.kwargs = dict(kwargs)
@@ -550,7 +630,21 @@ class Drone2dEnv:
         return o, r, done, d
 
     def render(self, mode="human", close=False):
-        return None
+        """``mode="rgb_array"``: the frame at the screen size, uint8 [screensize_y, screensize_x, 3],
+        with the flight path so far as the trail when ``render_path`` is set.  ``"human"``: None (no
+        window is opened)."""
+        if mode != "rgb_array":
+            return None
+        H, W = int(self.kwargs["screensize_y"]), int(self.kwargs["screensize_x"])
+        trails = None
+        if self.kwargs.get("render_path"):
+            cap = int(self.kwargs["n_steps"]) + 1
+            xy = np.zeros((1, cap, 2), np.float32)
+            fp = np.asarray(self.flight_path[-cap:], np.float64).reshape(-1, 2)  # (x, screen_height - y)
+            xy[0, :len(fp), 0] = fp[:, 0]
+            xy[0, :len(fp), 1] = float(self.kwargs["screensize_y"]) - fp[:, 1]
+            trails = (xy, np.array([len(fp)], np.int32))
+        return self._venv.render([0], size=(H, W), trails=trails)[0].cpu().numpy()
 
     def close(self):
         self._venv.close()

@@ -178,6 +178,7 @@ def run_first_episodes(venv, policy: MlpActor, *, deterministic: bool = False, s
         fl = np.stack([(xy[..., 0] + 1.0) * w / 2.0, h - (xy[..., 1] + 1.0) * h / 2.0], -1)
         fl[np.arange(steps)[:, None] >= out["time_spent"][None, :]] = np.nan  # after each episode's end
         out["flight_xy"] = fl
+        out["screen"] = (w, h)
     return out
 
 
@@ -195,6 +196,70 @@ def flight_path_lists(m: dict) -> list:
     return [fl[:T, j].tolist() for j, T in enumerate(m["time_spent"])]
 
 
+def flight_path_colours(m: dict) -> np.ndarray:
+    """uint8 [episodes, 3], main.py:374-383: red for a collided episode (and for a single episode),
+    else ``red_blue_grad`` of the min-max-normalised total reward."""
+    from .render import red_blue_grad
+
+    rew = np.asarray(m["rewards"], np.float64)
+    n = len(rew)
+    rgb = np.zeros((n, 3), np.uint8)
+    if n == 0:
+        return rgb
+    lo, hi = float(rew.min()), float(rew.max())
+    for i in range(n):
+        if m["collisions"][i] == 1 or n == 1 or not hi > lo:
+            rgb[i] = (255, 0, 0)
+        else:
+            rgb[i] = red_blue_grad((rew[i] - lo) / (hi - lo))
+    return rgb
+
+
+def plot_inputs(m: dict):
+    """What the plot is drawn from: (xy float32 [steps, episodes, 2] world positions, lengths int32
+    [episodes], rgb uint8 [episodes, 3]) of a ``run_first_episodes(..., flight_paths=True)`` result."""
+    fl = np.asarray(m["flight_xy"], np.float64)
+    h = float(m.get("screen", (1300.0, 1300.0))[1])
+    xy = np.nan_to_num(np.stack([fl[..., 0], h - fl[..., 1]], -1), nan=0.0).astype(np.float32)
+    return xy, np.asarray(m["time_spent"], np.int32), flight_path_colours(m)
+
+
+def _plot_scenario(venv_or_scenario, screen):
+    from .config import TEST_SCENARIOS
+    from .scenarios import Scenario, create_test_scenario
+
+    s = venv_or_scenario
+    if s is None or isinstance(s, (Scenario, abi.D2DScn)):
+        return s
+    if isinstance(s, str):  # a test scenario's name; 'stage_k' and the like have no fixed picture
+        return create_test_scenario(s, int(screen[0]), int(screen[1])) if s in TEST_SCENARIOS else None
+    return s.scenarios[0] if getattr(s, "scenarios", None) else None  # a batch: its (first) scenario
+
+
+def plot_flight_paths(m: dict, venv_or_scenario=None, size=None, device=None) -> np.ndarray:
+    """The reference's overview plot (main.py:329-389) of a ``run_first_episodes(..., flight_paths=True)``
+    result, drawn on the device by libd2d_render.so: uint8 [H, W, 3].  ``venv_or_scenario``: the batch
+    the episodes ran on, a Scenario / ABI record, a test scenario's name, or None for a blank
+    background (the reference's 'stage_k' case); ``size``: an int or (H, W), default the screen."""
+    from . import render as R
+
+    screen = m.get("screen", (1300.0, 1300.0))
+    if size is None:
+        size = (int(screen[1]), int(screen[0]))
+    dev = device if device is not None else getattr(venv_or_scenario, "device", None)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    xy, lens, rgb = plot_inputs(m)
+    rec = _plot_scenario(venv_or_scenario, screen)
+    r = R.Renderer(dev, max_frames=1)
+    try:
+        img = r.plot_paths(r.scn_tensor([rec]) if rec is not None else None, torch.from_numpy(xy),
+                           torch.from_numpy(lens), torch.from_numpy(rgb), size=size, screen=screen)
+        return img.cpu().numpy()
+    finally:
+        r.close()
+
+
 def summary(m: dict) -> dict:
     """The numbers of the reference's results.txt (main.py:318-325)."""
     runs = m["successes"] + m["fails"]
@@ -207,13 +272,19 @@ def summary(m: dict) -> dict:
 
 def write_results(m: dict, out_dir: str, scenario: str, agent_nr: str, agent_path: str):
     """The reference's per-scenario files: results.txt + collisions/rewards/apes/time_spent .npy
-    (+ the ``flight_paths`` JSON when ``m`` carries them), main.py:307-326."""
+    (+ the ``flight_paths`` JSON when ``m`` carries them, and then, with a HIP device to draw it on,
+    the overview plot ``plots/<scenario>.png``), main.py:307-389."""
     os.makedirs(out_dir, exist_ok=True)
     for k in ("collisions", "rewards", "apes", "time_spent"):
         np.save(os.path.join(out_dir, f"{k}.npy"), m[k])
     if "flight_xy" in m:
         with open(os.path.join(out_dir, "flight_paths"), "w") as f:
             json.dump(flight_path_lists(m), f)
+        if torch.cuda.is_available():  # the overview plot, main.py:329-389 (drawn on the device)
+            from .render import write_png
+
+            os.makedirs(os.path.join(out_dir, "plots"), exist_ok=True)
+            write_png(os.path.join(out_dir, "plots", f"{scenario}.png"), plot_flight_paths(m, scenario))
     s = summary(m)
     with open(os.path.join(out_dir, f"{scenario}_{agent_nr}_results.txt"), "w") as f:
         for k in ("Successes", "Fails", "Collisions", "Success rate", "Collision rate", "Average APE",
@@ -223,5 +294,13 @@ def write_results(m: dict, out_dir: str, scenario: str, agent_nr: str, agent_pat
     return s
 
 
+def save_gif(frames, path: str, fps: int = 60) -> None:
+    """Frames [T, H, W, 3] as an animated GIF (the reference's per-scenario GIF, main.py:283-300);
+    needs Pillow and raises ImportError without it."""
+    from .render import save_gif as _save
+
+    _save(frames, path, fps)
+
+
 __all__ = ["MlpActor", "run_first_episodes", "flight_path_lists", "summary", "write_results",
-           "write_results_rank0"]
+           "write_results_rank0", "plot_flight_paths", "plot_inputs", "flight_path_colours", "save_gif"]

@@ -124,6 +124,21 @@ class SB3VecEnv(_Base):
     def close(self):
         self.venv.close()
 
+    def get_images(self, size=256):
+        """The frames of the first min(num_envs, 16) envs (``Drone2dVecEnv.render``), a list of uint8
+        [H, W, 3] arrays.  65 536 pictures are nobody's monitor: the cap keeps VecVideoRecorder and
+        ``render`` usable on large batches."""
+        frames = self.venv.render(size=size).cpu().numpy()
+        return [f for f in frames]
+
+    def render(self, mode=None):
+        """``mode="rgb_array"``: the tiled image of ``get_images()``; any other mode: None (no window)."""
+        if mode != "rgb_array":
+            return None
+        from .render import tile_images
+
+        return tile_images(np.stack(self.get_images()))
+
     def seed(self, seed=None):
         if seed is not None:
             self.venv.seed_value = int(seed)
