@@ -32,6 +32,10 @@ RENDER_SRC = os.path.join(PKG_DIR, "csrc", "render", "d2d_render.hip")
 RENDER_HDRS = [os.path.join(PKG_DIR, "csrc", "render", "d2d_raster.h"), os.path.join(PKG_DIR, "csrc", "d2d_pmath.h"),
                os.path.join(REPO, "include", "d2d_render.h"), os.path.join(REPO, "include", "drone2d.h")]
 RENDER_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_render.so")
+# the fused evaluation step (include/d2d_eval.h), a library of its own under csrc/eval/
+EVAL_SRC = os.path.join(PKG_DIR, "csrc", "eval", "d2d_eval.hip")
+EVAL_HDRS = [os.path.join(PKG_DIR, "csrc", "eval", "d2d_eval_math.h"), os.path.join(REPO, "include", "d2d_eval.h")]
+EVAL_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_eval.so")
 
 # -ffp-contract=off: the kernels follow the reference's NumPy evaluation order (explicit fma() only
 # where NumPy/OpenBLAS fuses); no fast-math: IEEE inf/NaN semantics are part of the contract.
@@ -88,10 +92,19 @@ def build_render(force: bool = False, verbose: bool = False) -> str:
     return RENDER_OUT
 
 
+def build_eval(force: bool = False, verbose: bool = False) -> str:
+    """The evaluation step (libd2d_eval.so), with the PPO library's flags (float32 arithmetic, FMAs
+    contracted within an expression).  Compiled by ``build()`` or by the first evaluation that finds
+    it missing."""
+    if force or needs_build(EVAL_OUT, EVAL_SRC, EVAL_HDRS):
+        _compile(EVAL_SRC, EVAL_OUT, verbose, PPO_FLAGS)
+    return EVAL_OUT
+
+
 def build(force: bool = False, verbose: bool = False, exact: bool = False) -> str:
     """The in-tree libraries: the env (libdrone2d_hip.so: every mode, one scenario layout), the PPO
-    update kernels (libd2d_ppo.so), the renderer (libd2d_render.so) and, with ``exact``, the env's
-    exact-trig build."""
+    update kernels (libd2d_ppo.so), the renderer (libd2d_render.so), the evaluation step
+    (libd2d_eval.so) and, with ``exact``, the env's exact-trig build."""
     stale = os.path.join(PKG_DIR, "_lib", "libdrone2d_hip_rm.so")  # rounds 1-3's second layout build
     if os.path.exists(stale):
         os.remove(stale)
@@ -102,4 +115,5 @@ def build(force: bool = False, verbose: bool = False, exact: bool = False) -> st
     if force or needs_build(PPO_OUT, PPO_SRC, PPO_HDRS):
         _compile(PPO_SRC, PPO_OUT, verbose, PPO_FLAGS)
     build_render(force, verbose)
+    build_eval(force, verbose)
     return OUT

@@ -48,6 +48,15 @@ class MlpActor(torch.nn.Module):
         with np.load(path, allow_pickle=False) as z:
             return cls({k: z[k] for k in z.files}, batch_invariant=batch_invariant)
 
+    @classmethod
+    def from_policy(cls, actor_critic, batch_invariant: bool = False) -> "MlpActor":
+        """The actor of a ``ppo.ActorCritic`` (a copy of its policy net, ``action_net`` and ``log_std``):
+        a policy trained here through the torch loop."""
+        keep = ("mlp_extractor.policy_net.", "action_net.", "log_std")
+        sd = {k.replace(".", "_"): v.detach().cpu().numpy() for k, v in actor_critic.state_dict().items()
+              if k.startswith(keep)}
+        return cls(sd, batch_invariant=batch_invariant)
+
     @staticmethod
     def _lin_fixed(x: torch.Tensor, lin: torch.nn.Linear) -> torch.Tensor:
         y = lin.bias.expand(x.shape[0], -1).clone()

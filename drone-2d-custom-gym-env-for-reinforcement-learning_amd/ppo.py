@@ -23,11 +23,21 @@ At 65 536 envs a 2 048-step rollout would hold 134 M transitions, so GPU-scale r
 n_steps and enlarge batch_size (``PPOConfig.gpu_defaults``); the update rule is unchanged.  With
 ``torch.distributed`` initialised (one process per GPU, each with its env shard,
 ``drone2d_amd.shard``), gradients are averaged over ranks before each optimiser step (RCCL).
+
+Agent files (``PPO.save`` / ``PPO.load`` / ``ActorCritic.from_sb3_zip``, ``Checkpoint``): a zip laid out
+like SB3's -- ``policy.pth`` is the policy's state_dict under SB3's names -- whose other members carry
+what a resumed run needs (optimiser moments, noise generator, the rollout's carried observations, the
+env batch's state).  Every member holds tensors or JSON only (``torch.load(weights_only=True)``).
 """
 from __future__ import annotations
 
+import dataclasses
+import io
+import json
 import math
+import os
 import time
+import zipfile
 from dataclasses import dataclass
 
 import numpy as np
@@ -58,7 +68,42 @@ class PPOConfig:
         return cls(**dict(dict(n_steps=16, batch_size=32768), **over))
 
 
+@dataclass
+class Checkpoint:
+    """``PPO.learn(checkpoint=...)``: save ``<save_path>/<name_prefix>_<num_timesteps>_steps.zip`` whenever
+    ``num_timesteps`` crosses a multiple of ``save_freq`` -- SB3's CheckpointCallback file names, which
+    the reference reads back as its curriculum clock (main.py:161-177, drone_2d_env.py:76-86)."""
+    save_freq: int
+    save_path: str
+    name_prefix: str = "rl_model"
+
+
+AGENT_FORMAT_VERSION = 1
+AGENT_MEMBERS = ("data.json", "policy.pth", "train_state.pth", "env_state.pth")
+
 _HALF_LOG_2PI = 0.5 * math.log(2.0 * math.pi)
+
+
+def _zip_tensors(z: zipfile.ZipFile, name: str) -> dict:
+    return torch.load(io.BytesIO(z.read(name)), map_location="cpu", weights_only=True)
+
+
+def _to_tensors(x):
+    """A checkpoint value with every NumPy array as a tensor (so the member loads weights_only)."""
+    if isinstance(x, dict):
+        return {k: _to_tensors(v) for k, v in x.items()}
+    if isinstance(x, torch.Tensor):
+        return x.detach().cpu()
+    if isinstance(x, np.ndarray):
+        return torch.from_numpy(np.ascontiguousarray(x))
+    return x
+
+
+def _to_arrays(sd: dict) -> dict:
+    """An ``env_state.pth`` member as ``Drone2dVecEnv.load_state_dict`` takes it: the nested tables
+    (curriculum pool, fresh-curriculum recipes) back as NumPy arrays, the state tensors as they are."""
+    return {k: ({kk: (vv.numpy() if isinstance(vv, torch.Tensor) else vv) for kk, vv in v.items()}
+                if isinstance(v, dict) else v) for k, v in sd.items()}
 
 
 class ActorCritic(nn.Module):
@@ -115,6 +160,27 @@ class ActorCritic(nn.Module):
             sd = {k: torch.as_tensor(z[k]) for k in z.files}
         names = {n.replace(".", "_"): n for n in m.state_dict()}
         m.load_state_dict({names[k]: v for k, v in sd.items()}, strict=False)
+        return m
+
+    @classmethod
+    def from_sb3_zip(cls, path: str) -> "ActorCritic":
+        """The policy of an agent zip: ``policy.pth`` of a file written by ``PPO.save`` or by SB3's
+        ``PPO.save`` (the reference's ``ppo_agents/*.zip``).  The actor must be complete; the value
+        net is loaded when the file has one, and keeps its fresh init otherwise."""
+        with zipfile.ZipFile(path) as z:
+            if "policy.pth" not in z.namelist():
+                raise ValueError(f"{path}: no policy.pth member")
+            sd = _zip_tensors(z, "policy.pth")
+        m = cls()
+        own = m.state_dict()
+        actor = [k for k in own if k.startswith(("mlp_extractor.policy_net.", "action_net.", "log_std"))]
+        missing = [k for k in actor if k not in sd]
+        if missing:
+            raise ValueError(f"{path}: policy.pth lacks {missing}")
+        bad = [k for k in own if k in sd and tuple(sd[k].shape) != tuple(own[k].shape)]
+        if bad:
+            raise ValueError(f"{path}: policy.pth is not an MlpPolicy 27-64-64 (shape of {bad})")
+        m.load_state_dict({k: v.float() for k, v in sd.items() if k in own}, strict=False)
         return m
 
 
@@ -485,6 +551,7 @@ class PPO:
                  device=None):
         self.venv = venv
         self.cfg = config or PPOConfig()
+        self.seed = int(seed)
         self.device = torch.device(device) if device is not None else torch.device(venv.device)
         torch.manual_seed(seed)
         self.policy = (policy or ActorCritic()).to(self.device)
@@ -525,6 +592,8 @@ class PPO:
         self._upd_warm = False
         self._adv_ws = None      # every minibatch's advantage-statistics partials (_train_body_hip)
         self._fused = None       # decided at the first rollout (_alloc_rollout)
+        self._predict_t = 0      # predict()'s call counter: the Philox step index of its noise
+        self._predict_gen = None
 
     # ------------------------------------------------------------------ rollout
     def _alloc_rollout(self):
@@ -795,10 +864,13 @@ class PPO:
                 n_upd += 1
         return {k: float(v) / max(n_upd, 1) for k, v in self._acc.items()}
 
-    def learn(self, total_timesteps: int, log=None) -> list[dict]:
-        """Alternate rollouts and updates until ``total_timesteps`` env steps (this rank)."""
+    def learn(self, total_timesteps: int, log=None, checkpoint: Checkpoint | None = None) -> list[dict]:
+        """Alternate rollouts and updates until ``total_timesteps`` env steps (this rank);
+        ``checkpoint``: save the agent whenever ``num_timesteps`` crosses a multiple of its
+        ``save_freq`` (after the update, so a resumed run continues with the next rollout)."""
         hist = []
         while self.num_timesteps < total_timesteps:
+            before = self.num_timesteps
             t0 = time.perf_counter()
             ro = self.collect_rollouts()
             if self.device.type == "cuda":
@@ -813,7 +885,115 @@ class PPO:
             hist.append(rec)
             if log:
                 log(rec)
+            if checkpoint is not None and self.num_timesteps // checkpoint.save_freq > before // checkpoint.save_freq:
+                os.makedirs(checkpoint.save_path, exist_ok=True)
+                self.save(os.path.join(checkpoint.save_path,
+                                       f"{checkpoint.name_prefix}_{self.num_timesteps}_steps.zip"))
         return hist
 
+    # ------------------------------------------------------------------ predict / save / load
+    @torch.no_grad()
+    def predict(self, obs, deterministic: bool = False) -> torch.Tensor:
+        """The clipped actions for ``obs`` [n, 27] (SB3 ``model.predict``; stochastic by default, as the
+        reference calls it).  On a HIP device the evaluation library's act half (``evaluate.act``): call
+        k's noise for row i is the Philox draw of (seed, i, k); on the CPU the same in torch."""
+        x = torch.as_tensor(obs, dtype=torch.float32).to(self.device).reshape(-1, 27)
+        if self.device.type == "cuda":
+            from . import evaluate
 
-__all__ = ["PPOConfig", "ActorCritic", "ManualStep", "PPO", "compute_gae"]
+            a = evaluate.act(self.policy, x, deterministic=deterministic, seed=self.seed, t=self._predict_t)
+        else:
+            a = self.policy(x)[0]
+            if not deterministic:
+                if self._predict_gen is None:
+                    self._predict_gen = torch.Generator(device=self.device).manual_seed(self.seed + 7)
+                a = a + self.policy.log_std.exp() * torch.randn(a.shape, generator=self._predict_gen)
+            a = a.clamp(-1.0, 1.0)
+        if not deterministic:
+            self._predict_t += 1
+        return a
+
+    def _train_state(self) -> dict:
+        ts = {"gen": self.gen.get_state(), "perm_ctr": self._perm_ctr}
+        if self.manual is not None:
+            ts.update(m=self.manual.m, v=self.manual.v, t=self.manual.t)
+        else:
+            ts["opt"] = self.opt.state_dict()
+        if self._ro is not None:
+            ts["last_obs"] = self._ro["obs_cur"] if self._fused else self._ro["obs"][0]
+            ts["start0"] = self._ro["start0"]
+        return _to_tensors(ts)
+
+    def save(self, path: str) -> str:
+        """Write the agent as a zip laid out like SB3's: ``policy.pth`` (the policy's state_dict under
+        SB3's names), ``train_state.pth`` (Adam moments and step counter, the rollout noise generator,
+        the shuffle counter, the rollout's carried observations and episode starts), ``env_state.pth``
+        (``venv.state_dict()``, when the batch has one) and ``data.json`` (format version, PPOConfig,
+        num_timesteps, n_envs, seed).  Tensors and JSON only."""
+        if self.device.type == "cuda":
+            torch.cuda.synchronize(self.device)
+        members = {"policy.pth": _to_tensors(dict(self.policy.state_dict())), "train_state.pth": self._train_state()}
+        if hasattr(self.venv, "state_dict"):
+            members["env_state.pth"] = _to_tensors(self.venv.state_dict())
+        data = {"format_version": AGENT_FORMAT_VERSION, "config": dataclasses.asdict(self.cfg),
+                "num_timesteps": int(self.num_timesteps), "n_envs": self.n_envs, "seed": self.seed}
+        d = os.path.dirname(os.path.abspath(path))
+        os.makedirs(d, exist_ok=True)
+        tmp = path + ".part"
+        with zipfile.ZipFile(tmp, "w", zipfile.ZIP_STORED) as z:
+            z.writestr("data.json", json.dumps(data, indent=1))
+            for name, obj in members.items():
+                buf = io.BytesIO()
+                torch.save(obj, buf)
+                z.writestr(name, buf.getvalue())
+        os.replace(tmp, path)
+        return path
+
+    @classmethod
+    def load(cls, path: str, venv, device=None, restore_env: bool = True) -> "PPO":
+        """The agent of ``save``'s file on ``venv``, ready to go on learning where the saved run
+        stopped: policy, optimiser state, noise generator and shuffle counter, ``num_timesteps``, the env
+        batch's state (``restore_env``, when the file has one and ``venv`` can take it) and the
+        rollout's carried observations, so the next ``collect_rollouts`` continues the running episodes
+        instead of resetting them.  The first rollout and update after a load run eagerly and the HIP
+        graphs are captured again on the usual schedule (a captured rollout reads the env's own
+        observation tensor at a fixed address, which the restored observations are not in)."""
+        with zipfile.ZipFile(path) as z:
+            names = set(z.namelist())
+            data = json.loads(z.read("data.json"))
+            if data.get("format_version") != AGENT_FORMAT_VERSION:
+                raise ValueError(f"{path}: agent format {data.get('format_version')}, expected {AGENT_FORMAT_VERSION}")
+            policy_sd = _zip_tensors(z, "policy.pth")
+            ts = _zip_tensors(z, "train_state.pth")
+            env_sd = _zip_tensors(z, "env_state.pth") if "env_state.pth" in names else None
+        if int(venv.num_envs) != int(data["n_envs"]):
+            raise ValueError(f"{path}: saved with {data['n_envs']} envs, the batch has {venv.num_envs}")
+        algo = cls(venv, PPOConfig(**data["config"]), seed=int(data["seed"]), device=device)
+        algo.policy.load_state_dict(policy_sd)  # in place: ManualStep's flat buffer holds the parameters
+        if algo.manual is not None:
+            if "m" not in ts:
+                raise ValueError(f"{path}: saved with the torch optimiser, config.manual says ManualStep")
+            algo.manual.m.copy_(ts["m"])
+            algo.manual.v.copy_(ts["v"])
+            algo.manual.t.copy_(ts["t"])
+        else:
+            algo.opt.load_state_dict(ts["opt"])
+        algo.gen.set_state(ts["gen"])
+        algo._perm_ctr.copy_(ts["perm_ctr"])
+        algo.num_timesteps = int(data["num_timesteps"])
+        if restore_env and env_sd is not None and hasattr(venv, "load_state_dict"):
+            venv.load_state_dict(_to_arrays(env_sd))
+        if "last_obs" in ts:
+            algo._alloc_rollout()
+            last_obs = ts["last_obs"].to(algo.device)
+            if algo._fused:
+                algo._ro["obs_cur"] = last_obs.contiguous()
+            else:
+                algo._ro["obs"][0].copy_(last_obs)
+            algo._ro["start0"].copy_(ts["start0"])
+            # collect_rollouts resets the envs when the batch's generation is not the one it last saw
+            algo._ro_gen = getattr(venv, "generation", None)
+        return algo
+
+
+__all__ = ["PPOConfig", "Checkpoint", "ActorCritic", "ManualStep", "PPO", "compute_gae"]

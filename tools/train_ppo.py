@@ -2,12 +2,17 @@
 """PPO training end-to-end on one MI355X (GPU box): the HIP env batch + drone2d_amd.ppo.
 
     python tools/train_ppo.py [--envs 65536] [--updates 30] [--scenario corridor | --curriculum]
+                              [--save AGENT.zip] [--checkpoint-every STEPS] [--resume AGENT.zip]
 
 One JSON line per update (timesteps, mean finished-episode return, losses, env-steps/s including
 the policy forward passes and the PPO update) into gpurun_out/ppo.jsonl and on stdout.
 ``--curriculum`` trains as the reference does (mode='train': a fresh curriculum scenario per
 reset, stage by the global step count, drone_2d_env.py:76-86 / 324-372), with the pool refreshed
 (and the stage advanced) every ``--refresh`` updates.
+``--save`` writes the trained agent (``PPO.save``; ``tools/test_agent.py`` tests it), ``--checkpoint-every``
+also ``<dir of --save, or ppo_agents/ in the working directory>/rl_model_<steps>_steps.zip`` whenever the step count crosses
+a multiple of STEPS (the reference's checkpoint names), ``--resume`` continues a saved run: policy,
+optimiser, noise streams and the env batch as they were (same --envs, --n-steps, --batch as saved).
 """
 from __future__ import annotations
 
@@ -35,13 +40,17 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--no-graph", action="store_true", help="eager minibatch updates (A/B against the HIP graph)")
     ap.add_argument("--autograd", action="store_true", help="autograd + torch Adam update (A/B against ManualStep)")
+    ap.add_argument("--save", default=None, metavar="PATH", help="write the trained agent here (PPO.save)")
+    ap.add_argument("--checkpoint-every", type=int, default=0, metavar="STEPS",
+                    help="also save rl_model_<steps>_steps.zip every STEPS env steps")
+    ap.add_argument("--resume", default=None, metavar="PATH", help="continue the run saved in this agent file")
     a = ap.parse_args()
 
     import torch
 
     import drone2d_amd as d2
     from drone2d_amd.config import ENV_TRAIN_CONFIG
-    from drone2d_amd.ppo import PPO, PPOConfig
+    from drone2d_amd.ppo import PPO, Checkpoint, PPOConfig
 
     torch.cuda.set_device(0)
     kw = dict(ENV_TRAIN_CONFIG, scenario=a.scenario)
@@ -53,23 +62,30 @@ def main():
     cfg = PPOConfig.gpu_defaults(n_steps=a.n_steps, batch_size=a.batch, n_epochs=a.epochs)
     cfg.graph = not a.no_graph
     cfg.manual = not a.autograd
-    algo = PPO(venv, cfg, seed=a.seed)
+    # a resumed run takes its configuration, seed and env state from the file
+    algo = PPO.load(a.resume, venv) if a.resume else PPO(venv, cfg, seed=a.seed)
+    ckpt = None
+    if a.checkpoint_every > 0:
+        ck_dir = os.path.dirname(os.path.abspath(a.save)) if a.save else "ppo_agents"
+        ckpt = Checkpoint(a.checkpoint_every, ck_dir)
     os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
     tag = ("_eager" if a.no_graph else "") + ("_autograd" if a.autograd else "")
     out = open(os.path.join(REPO, "gpurun_out", f"ppo{tag}.jsonl"), "w")
-    t0 = time.perf_counter()
+    t0, steps0 = time.perf_counter(), algo.num_timesteps
     for u in range(a.updates):
         if a.curriculum and a.pool > 0 and u and u % a.refresh == 0:
             # the reference's stage clock is the global step count (checkpoint names, :76-86)
             venv.refresh_curriculum(sim_num=algo.num_timesteps)
-        rec = algo.learn(algo.num_timesteps + a.n_steps * a.envs)[-1]
+        rec = algo.learn(algo.num_timesteps + algo.cfg.n_steps * a.envs, checkpoint=ckpt)[-1]
         rec.update(update=u, wall_s=time.perf_counter() - t0)
         line = json.dumps({k: (round(v, 6) if isinstance(v, float) else v) for k, v in rec.items()})
         print(line, flush=True)
         out.write(line + "\n")
-    total = algo.num_timesteps / (time.perf_counter() - t0)
-    print(json.dumps({"envs": a.envs, "updates": a.updates, "timesteps": algo.num_timesteps, "graph": algo.use_graph, "manual": cfg.manual,
+    total = (algo.num_timesteps - steps0) / (time.perf_counter() - t0)
+    print(json.dumps({"envs": a.envs, "updates": a.updates, "timesteps": algo.num_timesteps, "graph": algo.use_graph, "manual": algo.cfg.manual,
                       "env_steps_per_s_incl_learning": total}), flush=True)
+    if a.save:
+        print(json.dumps({"saved": algo.save(a.save)}), flush=True)
     venv.close()
 
 
