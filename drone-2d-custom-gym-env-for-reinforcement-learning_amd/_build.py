@@ -36,6 +36,10 @@ RENDER_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_render.so")
 EVAL_SRC = os.path.join(PKG_DIR, "csrc", "eval", "d2d_eval.hip")
 EVAL_HDRS = [os.path.join(PKG_DIR, "csrc", "eval", "d2d_eval_math.h"), os.path.join(REPO, "include", "d2d_eval.h")]
 EVAL_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_eval.so")
+# the episode monitor (include/d2d_monitor.h), a library of its own under csrc/monitor/
+MONITOR_SRC = os.path.join(PKG_DIR, "csrc", "monitor", "d2d_monitor.hip")
+MONITOR_HDRS = [os.path.join(REPO, "include", "d2d_monitor.h"), os.path.join(REPO, "include", "drone2d.h")]
+MONITOR_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_monitor.so")
 
 # -ffp-contract=off: the kernels follow the reference's NumPy evaluation order (explicit fma() only
 # where NumPy/OpenBLAS fuses); no fast-math: IEEE inf/NaN semantics are part of the contract.
@@ -101,10 +105,20 @@ def build_eval(force: bool = False, verbose: bool = False) -> str:
     return EVAL_OUT
 
 
+def build_monitor(force: bool = False, verbose: bool = False) -> str:
+    """The episode monitor (libd2d_monitor.so), with the env's flags (-ffp-contract=off: its sums are
+    plain IEEE additions in the order include/d2d_monitor.h states, which the host twin repeats).
+    Compiled by ``build()`` or by the first ``EpisodeMonitor`` on a HIP device that finds it missing."""
+    if force or needs_build(MONITOR_OUT, MONITOR_SRC, MONITOR_HDRS):
+        _compile(MONITOR_SRC, MONITOR_OUT, verbose)
+    return MONITOR_OUT
+
+
 def build(force: bool = False, verbose: bool = False, exact: bool = False) -> str:
     """The in-tree libraries: the env (libdrone2d_hip.so: every mode, one scenario layout), the PPO
     update kernels (libd2d_ppo.so), the renderer (libd2d_render.so), the evaluation step
-    (libd2d_eval.so) and, with ``exact``, the env's exact-trig build."""
+    (libd2d_eval.so), the episode monitor (libd2d_monitor.so) and, with ``exact``, the env's
+    exact-trig build."""
     stale = os.path.join(PKG_DIR, "_lib", "libdrone2d_hip_rm.so")  # rounds 1-3's second layout build
     if os.path.exists(stale):
         os.remove(stale)
@@ -116,4 +130,5 @@ def build(force: bool = False, verbose: bool = False, exact: bool = False) -> st
         _compile(PPO_SRC, PPO_OUT, verbose, PPO_FLAGS)
     build_render(force, verbose)
     build_eval(force, verbose)
+    build_monitor(force, verbose)
     return OUT

@@ -594,6 +594,7 @@ class PPO:
         self._fused = None       # decided at the first rollout (_alloc_rollout)
         self._predict_t = 0      # predict()'s call counter: the Philox step index of its noise
         self._predict_gen = None
+        self.monitor = None      # an EpisodeMonitor (set_monitor / learn(monitor=...)); None: off
 
     # ------------------------------------------------------------------ rollout
     def _alloc_rollout(self):
@@ -625,6 +626,38 @@ class PPO:
             self._ro["obs"][0].copy_(obs.to(self.device))
         self._ro["start0"].fill_(True)
 
+    def set_monitor(self, monitor=True):
+        """Attach an ``EpisodeMonitor`` (``True``: a new one for the env batch) or detach it (``None`` /
+        ``False``).  The rollout then digests every env step's outputs with one ``monitor.step`` and ends
+        with one ``monitor.flush``; the record gains ``monitor/*`` and ``train/explained_variance``.  A
+        monitor attached to a batch in mid-flight (after ``PPO.load``, or between two ``learn`` calls)
+        starts with ``live=0``: the episodes under way are counted as skipped, not logged with partial
+        sums.  A captured rollout is dropped and captured again on the usual schedule."""
+        if monitor is True:
+            if self.monitor is not None:
+                return self.monitor
+            from .monitor import EpisodeMonitor
+
+            monitor = EpisodeMonitor(self.venv, getattr(self.venv, "device", self.device))
+        elif monitor is False:
+            monitor = None
+        if monitor is self.monitor:
+            return monitor
+        if monitor is not None and monitor.n != self.n_envs:
+            raise ValueError(f"the monitor is for {monitor.n} envs, the batch has {self.n_envs}")
+        self.monitor = monitor
+        self._ro_graph = None
+        self._ro_warm = False
+        if monitor is not None and self._ro is not None:
+            monitor.reset(live=False)  # (a fresh run resets it with the envs, in collect_rollouts)
+        return monitor
+
+    def _reset_envs(self):
+        obs = self.venv.reset()
+        if self.monitor is not None:
+            self.monitor.reset()
+        return obs
+
     @torch.no_grad()
     def _rollout_body_fused(self):
         """_rollout_body as T + 1 libd2d_ppo.so launches around the T env steps: step t's launch runs
@@ -654,7 +687,11 @@ class PPO:
             _ok(lib.d2d_ppo_rollout_step(C.byref(r), wptr, st), "d2d_ppo_rollout_step")
             if t < T:
                 obs, rew, term, trunc, info = self.venv.step(R["act_env"])
+                if self.monitor is not None:
+                    self.monitor.step(term, trunc, info)
                 r.prev_rew, r.prev_term, r.prev_trunc, r.prev_info = ptr(rew), ptr(term), ptr(trunc), ptr(info)
+        if self.monitor is not None:
+            self.monitor.flush()
         R["obs_cur"] = obs  # T even: the same double-buffer slot as at the start
         R["fin"].copy_(R["stats"][..., 0].sum())
         R["ret"].copy_(R["stats"][..., 1].sum())
@@ -674,6 +711,8 @@ class PPO:
             logp = pol.log_prob(mean, actions)
             # SB3 clips to the Box bounds for the env only; the buffer keeps the unclipped action
             new_obs, rew, term, trunc, info = self.venv.step(actions.clamp(-1.0, 1.0))
+            if self.monitor is not None:
+                self.monitor.step(term, trunc, info)
             rew = rew.to(dev).float()
             trunc = trunc.to(dev)
             done = term.to(dev) | trunc
@@ -699,6 +738,8 @@ class PPO:
             dst.copy_(src)
         R["obs"][0].copy_(R["obs"][T])
         R["start0"].copy_(R["done"][T - 1])
+        if self.monitor is not None:
+            self.monitor.flush()
 
     def collect_rollouts(self) -> dict:
         T, N = self.cfg.n_steps, self.n_envs
@@ -709,11 +750,11 @@ class PPO:
             # and start the next rollout from a reset
             self._ro_graph = None
             self._ro_warm = False
-            self._set_first_obs(self.venv.reset())
+            self._set_first_obs(self._reset_envs())
         self._ro_gen = gen
         if self._ro is None:
             self._alloc_rollout()
-            self._set_first_obs(self.venv.reset())
+            self._set_first_obs(self._reset_envs())
         R = self._ro
         body = self._rollout_body_fused if self._fused else self._rollout_body
         R["fin"].zero_()
@@ -737,8 +778,28 @@ class PPO:
             body()
             self._ro_warm = True
         self.num_timesteps += T * N
-        f, r = float(R["fin"]), float(R["ret"])
-        return {"episodes": f, "mean_return": r / f if f else float("nan")}
+        if self.monitor is None:
+            f, r = float(R["fin"]), float(R["ret"])
+            return {"episodes": f, "mean_return": r / f if f else float("nan")}
+        # fin, ret, the explained variance and the flushed vector packed on the device and read with
+        # one copy, where fin and ret were read before
+        ev = self._explained_variance().to(torch.float64)
+        host = torch.cat([R["fin"].reshape(1), R["ret"].reshape(1), ev.reshape(1),
+                          self.monitor.out.to(self.device)]).cpu()
+        f, r = float(host[0]), float(host[1])
+        out = {"episodes": f, "mean_return": r / f if f else float("nan")}
+        out.update({"monitor/" + k: v for k, v in self.monitor.scalars(host[3:]).items()})
+        out["train/explained_variance"] = float(host[2])
+        return out
+
+    @torch.no_grad()
+    def _explained_variance(self) -> torch.Tensor:
+        """SB3's ``explained_variance(values, returns)`` over the rollout buffer, before the update:
+        1 - Var(returns - values) / Var(returns) (NaN when the returns do not vary)."""
+        val, ret = self._ro["val"].reshape(-1), self._flat[4]
+        var_y = torch.var(ret, unbiased=False)
+        return torch.where(var_y == 0, torch.full_like(var_y, float("nan")),
+                           1.0 - torch.var(ret - val, unbiased=False) / var_y)
 
     # ------------------------------------------------------------------ update
     def _minibatch(self, idx: torch.Tensor, zero_grad: bool = True, adv_ws=None):
@@ -864,10 +925,16 @@ class PPO:
                 n_upd += 1
         return {k: float(v) / max(n_upd, 1) for k, v in self._acc.items()}
 
-    def learn(self, total_timesteps: int, log=None, checkpoint: Checkpoint | None = None) -> list[dict]:
+    def learn(self, total_timesteps: int, log=None, checkpoint: Checkpoint | None = None, monitor=None,
+              logger=None) -> list[dict]:
         """Alternate rollouts and updates until ``total_timesteps`` env steps (this rank);
         ``checkpoint``: save the agent whenever ``num_timesteps`` crosses a multiple of its
-        ``save_freq`` (after the update, so a resumed run continues with the next rollout)."""
+        ``save_freq`` (after the update, so a resumed run continues with the next rollout).
+        ``monitor``: ``True`` or an ``EpisodeMonitor`` -- ``set_monitor`` it first (``None``: leave
+        things as they are; off unless one was set).  ``logger``: a ``trainlog.ScalarLog`` (anything
+        with ``log(record)``) that gets every record after ``log``."""
+        if monitor is not None:
+            self.set_monitor(monitor)
         hist = []
         while self.num_timesteps < total_timesteps:
             before = self.num_timesteps
@@ -885,6 +952,8 @@ class PPO:
             hist.append(rec)
             if log:
                 log(rec)
+            if logger is not None:
+                logger.log(rec)
             if checkpoint is not None and self.num_timesteps // checkpoint.save_freq > before // checkpoint.save_freq:
                 os.makedirs(checkpoint.save_path, exist_ok=True)
                 self.save(os.path.join(checkpoint.save_path,

@@ -3,6 +3,7 @@
 
     python tools/train_ppo.py [--envs 65536] [--updates 30] [--scenario corridor | --curriculum]
                               [--save AGENT.zip] [--checkpoint-every STEPS] [--resume AGENT.zip]
+                              [--log-dir DIR [--no-tensorboard]]
 
 One JSON line per update (timesteps, mean finished-episode return, losses, env-steps/s including
 the policy forward passes and the PPO update) into gpurun_out/ppo.jsonl and on stdout.
@@ -13,6 +14,9 @@ reset, stage by the global step count, drone_2d_env.py:76-86 / 324-372), with th
 also ``<dir of --save, or ppo_agents/ in the working directory>/rl_model_<steps>_steps.zip`` whenever the step count crosses
 a multiple of STEPS (the reference's checkpoint names), ``--resume`` continues a saved run: policy,
 optimiser, noise streams and the env batch as they were (same --envs, --n-steps, --batch as saved).
+``--log-dir`` attaches the episode monitor (drone2d_amd.monitor) and writes ``progress.csv``, a TensorBoard
+event file, ``env_train_config.txt`` and ``rl_config.txt`` there (drone2d_amd.trainlog; the reference's
+``tensorboard_log="logs"`` + ``TensorboardLogger``, main.py:192-208).
 """
 from __future__ import annotations
 
@@ -44,6 +48,10 @@ def main():
     ap.add_argument("--checkpoint-every", type=int, default=0, metavar="STEPS",
                     help="also save rl_model_<steps>_steps.zip every STEPS env steps")
     ap.add_argument("--resume", default=None, metavar="PATH", help="continue the run saved in this agent file")
+    ap.add_argument("--log-dir", default=None, metavar="DIR",
+                    help="monitor the episodes on the device and write progress.csv, a TensorBoard event file and "
+                         "the two config files here")
+    ap.add_argument("--no-tensorboard", action="store_true", help="with --log-dir: progress.csv only")
     a = ap.parse_args()
 
     import torch
@@ -71,17 +79,28 @@ def main():
     os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
     tag = ("_eager" if a.no_graph else "") + ("_autograd" if a.autograd else "")
     out = open(os.path.join(REPO, "gpurun_out", f"ppo{tag}.jsonl"), "w")
+    logger = None
+    if a.log_dir:
+        import dataclasses
+
+        from drone2d_amd.trainlog import ScalarLog
+
+        logger = ScalarLog(a.log_dir, tensorboard=not a.no_tensorboard)
+        logger.write_configs(kw, dataclasses.asdict(algo.cfg))
+        algo.set_monitor(True)
     t0, steps0 = time.perf_counter(), algo.num_timesteps
     for u in range(a.updates):
         if a.curriculum and a.pool > 0 and u and u % a.refresh == 0:
             # the reference's stage clock is the global step count (checkpoint names, :76-86)
             venv.refresh_curriculum(sim_num=algo.num_timesteps)
-        rec = algo.learn(algo.num_timesteps + algo.cfg.n_steps * a.envs, checkpoint=ckpt)[-1]
+        rec = algo.learn(algo.num_timesteps + algo.cfg.n_steps * a.envs, checkpoint=ckpt, logger=logger)[-1]
         rec.update(update=u, wall_s=time.perf_counter() - t0)
         line = json.dumps({k: (round(v, 6) if isinstance(v, float) else v) for k, v in rec.items()})
         print(line, flush=True)
         out.write(line + "\n")
     total = (algo.num_timesteps - steps0) / (time.perf_counter() - t0)
+    if logger is not None:
+        logger.close()
     print(json.dumps({"envs": a.envs, "updates": a.updates, "timesteps": algo.num_timesteps, "graph": algo.use_graph, "manual": algo.cfg.manual,
                       "env_steps_per_s_incl_learning": total}), flush=True)
     if a.save:
