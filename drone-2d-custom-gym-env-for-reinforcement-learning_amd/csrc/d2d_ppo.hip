@@ -76,26 +76,32 @@ struct HeadArgs {
     float* ls_grad;
     float *acc_pl, *acc_vl, *acc_ent, *acc_clip;
 };
-__device__ __forceinline__ void head_finish_body(const HeadArgs& H) {
-    __shared__ double red[5 * 4];
+// NK = 5: the head rows of the entry points without control.  NK = 6 (the control path,
+// d2d_ppo_grad_reduce_ctl): a sixth column, sum((ratio - 1) - log_ratio), and the control block's
+// counters -- plain stores from the one thread that also adds the statistics, so the order is fixed.
+template <int NK>
+__device__ __forceinline__ void head_finish_body(const HeadArgs& H, d2d_ppo_ctl* ctl = nullptr) {
+    __shared__ double red[NK * 4];
     const int m = H.m, nb = H.nb;
     const float* partial = H.partial;
-    double t[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    double t[NK];
+#pragma unroll
+    for (int k = 0; k < NK; ++k) t[k] = 0.0;
     int b = threadIdx.x;
     for (; b + 3 * 256 < nb; b += 4 * 256) {  // four rows' loads in flight
-        float v[4][5];
+        float v[4][NK];
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
-            for (int k = 0; k < 5; ++k) v[u][k] = partial[(size_t)(b + u * 256) * 5 + k];
+            for (int k = 0; k < NK; ++k) v[u][k] = partial[(size_t)(b + u * 256) * NK + k];
 #pragma unroll
         for (int u = 0; u < 4; ++u)
 #pragma unroll
-            for (int k = 0; k < 5; ++k) t[k] += v[u][k];
+            for (int k = 0; k < NK; ++k) t[k] += v[u][k];
     }
     for (; b < nb; b += 256) {
 #pragma unroll
-        for (int k = 0; k < 5; ++k) t[k] += partial[(size_t)b * 5 + k];
+        for (int k = 0; k < NK; ++k) t[k] += partial[(size_t)b * NK + k];
     }
     block_sum_n(t, red);
     if (threadIdx.x == 0) {
@@ -105,9 +111,25 @@ __device__ __forceinline__ void head_finish_body(const HeadArgs& H) {
         *H.acc_vl += (float)(t[1] / m);
         *H.acc_clip += (float)(t[2] / m);
         *H.acc_ent += (0.5f + HALF_LOG_2PI + H.log_std[0]) + (0.5f + HALF_LOG_2PI + H.log_std[1]);
+        if constexpr (NK == 6) {
+            const float kl = (float)(t[5] / m);
+            ctl->count += 1;
+            ctl->kl_last = kl;
+            ctl->kl_sum += kl;
+        }
     }
 }
-__global__ __launch_bounds__(256) void head_finish_kernel(HeadArgs H) { head_finish_body(H); }
+__global__ __launch_bounds__(256) void head_finish_kernel(HeadArgs H) { head_finish_body<5>(H); }
+
+// the first node of a controlled update
+__global__ void ctl_reset_kernel(d2d_ppo_ctl* ctl) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) {
+        ctl->stop = 0;
+        ctl->count = 0;
+        ctl->kl_sum = 0.0f;
+        ctl->kl_last = 0.0f;
+    }
+}
 
 // ------------------------------------------------------------------ per-sample MLP passes
 // blockIdx.y = 0: the policy net (27-64-64 tanh -> 2), 1: the value net (-> 1); the activations are
@@ -626,14 +648,39 @@ struct FusedArgs {
     int row_len;
     float* hpart;  // [2 gridDim.x][5]
 };
+// CTL (d2d_ppo_fused_grad_ctl): clip and clip_vf come from the control block, the value head clips
+// its prediction around old_val, the policy head's row has a sixth sum (the KL estimate), and a
+// stopped update's workgroups return before their first barrier.  CTL = false is the kernel as it
+// was: same arguments, same code.
+template <bool CTL>
+struct FusedKArgs {
+    FusedArgs a;
+};
+template <>
+struct FusedKArgs<true> {
+    FusedArgs a;
+    const d2d_ppo_ctl* ctl;
+    const float* old_val;  // the rollout's stored values
+};
 constexpr int FG_SPC = 64;
-__global__ __launch_bounds__(256, 2) void mlp_fused_grad_kernel(FusedArgs A) {
+template <bool CTL>
+__global__ __launch_bounds__(256, 2) void mlp_fused_grad_kernel(FusedKArgs<CTL> K) {
+    const FusedArgs& A = K.a;
+    constexpr int NQ = CTL ? 6 : 5;  // head sums per row
+    // the stop flag is read first and acted on once the operand loads below are in flight (still
+    // ahead of the first barrier; it is uniform over the grid), so the read costs no round trip
+    float clip_vf = -1.0f;
+    int stop = 0;
+    if constexpr (CTL) {
+        stop = K.ctl->stop;
+        clip_vf = K.ctl->clip_vf;
+    }
     __shared__ float xs[FG_SPC][XS];
     __shared__ float h1s[FG_SPC][HS], h2s[FG_SPC][HS], g1s[FG_SPC][HS], g2s[FG_SPC][HS];
     __shared__ float gos[2][FG_SPC];
     __shared__ float w3s[2][HID + 1];  // output rows, bias in column HID
     __shared__ int64_t rows[FG_SPC];
-    __shared__ double red[5 * 4];
+    __shared__ double red[NQ * 4];
     const int net = blockIdx.y;
     const FusedNet& N = A.net[net];
     const int od = N.od, m = A.m;
@@ -654,6 +701,9 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_grad_kernel(FusedArgs A) {
         }
 #pragma unroll
         for (int c = 0; c < NW2; ++c) v2[c] = N.w2[c * 256 + tid];
+        if constexpr (CTL) {
+            if (stop != 0) return;
+        }
 #pragma unroll
         for (int c = 0; c < NW1; ++c) {
             const int e = c * 256 + tid;
@@ -695,7 +745,15 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_grad_kernel(FusedArgs A) {
     const float ls0 = A.log_std[0], ls1 = A.log_std[1], is0 = expf(-ls0), is1 = expf(-ls1);
     f32x16 dw2 = {}, dw1 = {};
     float db1 = 0.0f, db2 = 0.0f, dw3a = 0.0f, dw3b = 0.0f, db3a = 0.0f, db3b = 0.0f;
-    double q[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
+    double q[NQ];
+#pragma unroll
+    for (int k = 0; k < NQ; ++k) q[k] = 0.0;
+    float clip;
+    if constexpr (CTL) {
+        clip = K.ctl->clip;
+    } else {
+        clip = A.clip;
+    }
     const int nch = (m + FG_SPC - 1) / FG_SPC;
     PPO_STAMP(1);
     for (int c = blockIdx.x; c < nch; c += gridDim.x) {
@@ -761,18 +819,28 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_grad_kernel(FusedArgs A) {
                         const float logp =
                             (-0.5f * z0 * z0 - ls0 - HALF_LOG_2PI) + (-0.5f * z1 * z1 - ls1 - HALF_LOG_2PI);
                         const float a = A.normalize ? (A.adv[j] - adv_mean) * adv_inv : A.adv[j];
-                        const float ratio = expf(logp - A.old_logp[j]);
-                        const float s1 = a * ratio, s2 = a * fminf(fmaxf(ratio, 1.0f - A.clip), 1.0f + A.clip);
+                        const float log_ratio = logp - A.old_logp[j];
+                        const float ratio = expf(log_ratio);
+                        const float s1 = a * ratio, s2 = a * fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
                         const float g_lp = (s1 <= s2) ? a * ratio * (-1.0f / m) : 0.0f;
                         g0 = g_lp * z0 * is0;
                         g1v = g_lp * z1 * is1;
                         q[0] += fminf(s1, s2);
-                        q[2] += fabsf(ratio - 1.0f) > A.clip ? 1.0 : 0.0;
+                        q[2] += fabsf(ratio - 1.0f) > clip ? 1.0 : 0.0;
                         q[3] += (double)g_lp * (z0 * z0 - 1.0f);
                         q[4] += (double)g_lp * (z1 * z1 - 1.0f);
+                        if constexpr (CTL) q[5] += (double)((ratio - 1.0f) - log_ratio);
                     } else {
-                        const float err = A.ret[j] - o0;
-                        g0 = err * (-2.0f * A.vf_coef / m);
+                        float err = A.ret[j] - o0;
+                        bool pass = true;
+                        if constexpr (CTL) {
+                            if (clip_vf >= 0.0f) {  // SB3 clip_range_vf: the prediction clipped around the old value
+                                const float old = K.old_val[j], d = o0 - old;
+                                err = A.ret[j] - (old + fminf(fmaxf(d, -clip_vf), clip_vf));
+                                pass = fabsf(d) <= clip_vf;  // torch.clamp's gradient: bounds included
+                            }
+                        }
+                        g0 = pass ? err * (-2.0f * A.vf_coef / m) : 0.0f;
                         q[1] += (double)err * err;
                     }
                 }
@@ -863,18 +931,23 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_grad_kernel(FusedArgs A) {
     }
     block_sum_n(q, red);
     if (tid == 0) {
-        float* o = A.hpart + ((size_t)net * gridDim.x + blockIdx.x) * 5;
+        float* o = A.hpart + ((size_t)net * gridDim.x + blockIdx.x) * NQ;
 #pragma unroll
-        for (int k = 0; k < 5; ++k) o[k] = (float)q[k];
+        for (int k = 0; k < NQ; ++k) o[k] = (float)q[k];
     }
     PPO_STAMP(7);
 }
 
 constexpr int ADAM_THREADS = 1024, ADAM_PER_THREAD = 16;  // n <= 16 384 parameters
-__global__ __launch_bounds__(ADAM_THREADS) void adam_kernel(int n, float* __restrict__ p, float* __restrict__ g,
-                                                            float* __restrict__ m1, float* __restrict__ m2,
-                                                            float* __restrict__ t, float lr, float b1, float b2,
-                                                            float eps, float max_norm) {
+// CTL (d2d_ppo_adam_ctl): SB3's target_kl check sits here, after the statistics were recorded and
+// (multi-rank) after kl_last became the rank mean, and lr comes from the control block.  Every thread
+// reads the flag and the KL next to its gradient loads and all of them leave together, ahead of the
+// step's barriers and stores; a thread that reads `stop` after thread 0 has set it leaves all the same.
+template <bool CTL>
+__device__ __forceinline__ void adam_body(int n, float* __restrict__ p, float* __restrict__ g,
+                                          float* __restrict__ m1, float* __restrict__ m2, float* __restrict__ t,
+                                          float lr, float b1, float b2, float eps, float max_norm,
+                                          d2d_ppo_ctl* ctl = nullptr) {
     __shared__ double red[ADAM_THREADS / 64];
     // the moments and parameters are loaded with the gradient, ahead of the norm's reduction, so
     // the update below waits on no memory
@@ -887,6 +960,16 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_kernel(int n, float* __rest
         a0v[k] = in ? m1[i] : 0.0f;
         v0v[k] = in ? m2[i] : 0.0f;
         p0v[k] = in ? p[i] : 0.0f;
+    }
+    if constexpr (CTL) {
+        const int stop = ctl->stop;
+        const float kl = ctl->kl_last, limit = ctl->kl_limit;
+        lr = ctl->lr;
+        if (stop != 0) return;
+        if (kl > limit) {
+            if (threadIdx.x == 0) ctl->stop = 1;
+            return;
+        }
     }
     double q = 0.0;
 #pragma unroll
@@ -913,6 +996,18 @@ __global__ __launch_bounds__(ADAM_THREADS) void adam_kernel(int n, float* __rest
     }
     __syncthreads();
     if (threadIdx.x == 0) t[0] = step;
+}
+__global__ __launch_bounds__(ADAM_THREADS) void adam_kernel(int n, float* __restrict__ p, float* __restrict__ g,
+                                                            float* __restrict__ m1, float* __restrict__ m2,
+                                                            float* __restrict__ t, float lr, float b1, float b2,
+                                                            float eps, float max_norm) {
+    adam_body<false>(n, p, g, m1, m2, t, lr, b1, b2, eps, max_norm);
+}
+__global__ __launch_bounds__(ADAM_THREADS) void adam_ctl_kernel(int n, float* __restrict__ p, float* __restrict__ g,
+                                                                float* __restrict__ m1, float* __restrict__ m2,
+                                                                float* __restrict__ t, float b1, float b2, float eps,
+                                                                float max_norm, d2d_ppo_ctl* ctl) {
+    adam_body<true>(n, p, g, m1, m2, t, 0.0f, b1, b2, eps, max_norm, ctl);
 }
 
 // (A spread Adam -- ceil(n / 1024) workgroups, each computing the norm -- measured 8.1 us + 3.9 us for
@@ -1029,7 +1124,19 @@ __global__ __launch_bounds__(256) void wgrad_reduce_kernel(int n_chunks, int row
     // with H.partial set, the last workgroup finishes the loss head (head_finish_kernel's work) and
     // writes log_std's two gradient slots, which the reduce then leaves alone
     if (H.partial != nullptr && blockIdx.x == gridDim.x - 1) {
-        head_finish_body(H);
+        head_finish_body<5>(H);
+    } else {
+        wgrad_reduce_body(n_chunks, row_len, partial, g, H);
+    }
+}
+// d2d_ppo_grad_reduce_ctl: the same over [nb][6] head rows, and nothing once the update has stopped
+// (`stop` is written by adam_ctl_kernel alone, a launch of its own, so every workgroup sees one value)
+__global__ __launch_bounds__(256) void grad_reduce_ctl_kernel(int n_chunks, int row_len,
+                                                              const float* __restrict__ partial, float* __restrict__ g,
+                                                              HeadArgs H, d2d_ppo_ctl* ctl) {
+    if (ctl->stop != 0) return;
+    if (blockIdx.x == gridDim.x - 1) {
+        head_finish_body<6>(H, ctl);
     } else {
         wgrad_reduce_body(n_chunks, row_len, partial, g, H);
     }
@@ -1158,15 +1265,14 @@ int32_t d2d_ppo_fused_rows(int32_t m) {
     return nch < n_cus() ? nch : n_cus();
 }
 
-int32_t d2d_ppo_fused_grad(int32_t m, const int64_t* idx, const float* obs, const float* act, const float* old_logp,
-                           const float* adv, const float* ret, const float* log_std, const double* ws, int32_t normalize,
-                           float clip, float vf_coef, const float* const* weights, const int32_t* offsets,
-                           int32_t row_len, float* wpart, float* hpart, void* stream) {
-    if (m <= 0) return 0;
+// d2d_ppo_fused_grad's argument checks and kernel arguments (shared with d2d_ppo_fused_grad_ctl)
+static int32_t fused_args(FusedArgs& A, int32_t m, const int64_t* idx, const float* obs, const float* act,
+                          const float* old_logp, const float* adv, const float* ret, const float* log_std,
+                          const double* ws, int32_t normalize, float clip, float vf_coef, const float* const* weights,
+                          const int32_t* offsets, int32_t row_len, float* wpart, float* hpart) {
     if (!idx || !obs || !act || !old_logp || !adv || !ret || !log_std || !weights || !offsets || !wpart || !hpart ||
         (normalize && !ws))
         return (int32_t)hipErrorInvalidValue;
-    FusedArgs A{};
     for (int n = 0; n < 2; ++n) {
         const float* const* W = weights + 6 * n;
         A.net[n] = FusedNet{W[0], W[1], W[2], W[3], W[4], W[5], {0, 0, 0, 0, 0, 0}, n == 0 ? 2 : 1};
@@ -1193,7 +1299,69 @@ int32_t d2d_ppo_fused_grad(int32_t m, const int64_t* idx, const float* obs, cons
     A.wpart = wpart;
     A.row_len = row_len;
     A.hpart = hpart;
-    hipLaunchKernelGGL(mlp_fused_grad_kernel, dim3(d2d_ppo_fused_rows(m), 2), dim3(256), 0, (hipStream_t)stream, A);
+    return 0;
+}
+
+int32_t d2d_ppo_fused_grad(int32_t m, const int64_t* idx, const float* obs, const float* act, const float* old_logp,
+                           const float* adv, const float* ret, const float* log_std, const double* ws, int32_t normalize,
+                           float clip, float vf_coef, const float* const* weights, const int32_t* offsets,
+                           int32_t row_len, float* wpart, float* hpart, void* stream) {
+    if (m <= 0) return 0;
+    FusedKArgs<false> K{};
+    const int32_t e = fused_args(K.a, m, idx, obs, act, old_logp, adv, ret, log_std, ws, normalize, clip, vf_coef,
+                                 weights, offsets, row_len, wpart, hpart);
+    if (e != 0) return e;
+    hipLaunchKernelGGL(mlp_fused_grad_kernel<false>, dim3(d2d_ppo_fused_rows(m), 2), dim3(256), 0, (hipStream_t)stream,
+                       K);
+    return rc(hipGetLastError());
+}
+
+int32_t d2d_ppo_ctl_version(void) { return D2D_PPO_CTL_VERSION; }
+
+int32_t d2d_ppo_ctl_reset(d2d_ppo_ctl* ctl, void* stream) {
+    if (!ctl) return (int32_t)hipErrorInvalidValue;
+    hipLaunchKernelGGL(ctl_reset_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, ctl);
+    return rc(hipGetLastError());
+}
+
+int32_t d2d_ppo_fused_grad_ctl(int32_t m, const int64_t* idx, const float* obs, const float* act,
+                               const float* old_logp, const float* adv, const float* ret, const float* old_values,
+                               const float* log_std, const double* ws, int32_t normalize, float vf_coef,
+                               const float* const* weights, const int32_t* offsets, int32_t row_len, float* wpart,
+                               float* hpart, const d2d_ppo_ctl* ctl, void* stream) {
+    if (m <= 0) return 0;
+    if (!ctl || !old_values) return (int32_t)hipErrorInvalidValue;
+    FusedKArgs<true> K{};
+    const int32_t e = fused_args(K.a, m, idx, obs, act, old_logp, adv, ret, log_std, ws, normalize, 0.0f, vf_coef,
+                                 weights, offsets, row_len, wpart, hpart);
+    if (e != 0) return e;
+    K.ctl = ctl;
+    K.old_val = old_values;
+    hipLaunchKernelGGL(mlp_fused_grad_kernel<true>, dim3(d2d_ppo_fused_rows(m), 2), dim3(256), 0, (hipStream_t)stream,
+                       K);
+    return rc(hipGetLastError());
+}
+
+int32_t d2d_ppo_grad_reduce_ctl(int32_t n_rows, int32_t row_len, const float* partial, float* g, int32_t n_blocks,
+                                const float* head_partial, int32_t m, const float* log_std, float ent_coef,
+                                float* log_std_grad, float* acc_pl, float* acc_vl, float* acc_ent, float* acc_clip,
+                                d2d_ppo_ctl* ctl, void* stream) {
+    if (n_rows <= 0 || row_len <= 0) return 0;
+    if (!partial || !g || !head_partial || !log_std || !log_std_grad || log_std_grad < g ||
+        log_std_grad + 2 > g + row_len || !acc_pl || !acc_vl || !acc_ent || !acc_clip || !ctl || m <= 0)
+        return (int32_t)hipErrorInvalidValue;
+    const HeadArgs H{m, n_blocks, head_partial, log_std, ent_coef, log_std_grad, acc_pl, acc_vl, acc_ent, acc_clip};
+    hipLaunchKernelGGL(grad_reduce_ctl_kernel, dim3((row_len + 63) / 64 + 1), dim3(256), 0, (hipStream_t)stream,
+                       n_rows, row_len, partial, g, H, ctl);
+    return rc(hipGetLastError());
+}
+
+int32_t d2d_ppo_adam_ctl(int32_t n, float* p, float* g, float* m1, float* m2, float* t, float b1, float b2, float eps,
+                         float max_norm, d2d_ppo_ctl* ctl, void* stream) {
+    if (n <= 0) return 0;
+    if (n > ADAM_THREADS * ADAM_PER_THREAD || !ctl) return (int32_t)hipErrorInvalidValue;
+    hipLaunchKernelGGL(adam_ctl_kernel, dim3(1), dim3(ADAM_THREADS), 0, (hipStream_t)stream, n, p, g, m1, m2, t, b1,
+                       b2, eps, max_norm, ctl);
     return rc(hipGetLastError());
 }
 

@@ -17,7 +17,10 @@ this module restates the parts of SB3 2.1 that a training run executes, in the s
   never truncates: time-up is terminal, so this path is idle by default).
 * ``compute_returns_and_advantage`` (SB3 ``RolloutBuffer``): GAE(lambda) with episode starts.
 * ``train`` (SB3 ``PPO.train``): shuffled minibatches, per-minibatch advantage normalisation,
-  clipped surrogate, MSE value loss, entropy bonus, grad-norm clipping, Adam(eps=1e-5).
+  clipped surrogate, MSE value loss, entropy bonus, grad-norm clipping, Adam(eps=1e-5); with
+  ``PPOConfig.control`` also SB3's learning-rate / clip-range schedules (linear), ``clip_range_vf``,
+  ``approx_kl`` and the ``target_kl`` early stop, read from and decided in a device-resident
+  ``ControlBlock`` so that they work inside the captured update (DESIGN.md "PPO control").
 
 At 65 536 envs a 2 048-step rollout would hold 134 M transitions, so GPU-scale runs shorten
 n_steps and enlarge batch_size (``PPOConfig.gpu_defaults``); the update rule is unchanged.  With
@@ -61,6 +64,35 @@ class PPOConfig:
     normalize_advantage: bool = True
     graph: bool = True              # GPU, one rank: the minibatch update replayed as one HIP graph
     manual: bool = True             # MLP backward + Adam written out over flat buffers (ManualStep)
+    # PPO control (include/d2d_ppo.h "PPO control"); None = off.  Setting any of the four selects the
+    # control path: the update reads its coefficients from a device-resident control block, records
+    # approx_kl and can stop early on its own, also inside a captured HIP graph.
+    learning_rate_end: float | None = None  # linear schedule: x = end + (start - end) * progress_remaining
+    clip_range_end: float | None = None
+    clip_range_vf: float | None = None      # SB3 clip_range_vf: the value prediction clipped around old_values
+    target_kl: float | None = None          # SB3 target_kl; float("inf"): never stops, approx_kl logged only
+
+    def __post_init__(self):
+        for name in ("learning_rate", "clip_range"):
+            if callable(getattr(self, name)):
+                raise TypeError(f"PPOConfig.{name} is a callable: a schedule cannot be stored in an agent file; "
+                                f"give the start value as {name} and the final one as {name}_end (linear in SB3's "
+                                "progress_remaining)")
+
+    @property
+    def control(self) -> bool:
+        return any(x is not None for x in (self.learning_rate_end, self.clip_range_end, self.clip_range_vf,
+                                           self.target_kl))
+
+    def coefs(self, progress_remaining: float = 1.0) -> tuple:
+        """(lr, clip_range, clip_range_vf or -1.0, KL limit = 1.5 * target_kl or +inf) of an update at
+        SB3's ``progress_remaining`` (1 at the start of a run, 0 at its end)."""
+        def lin(start, end):
+            return start if end is None else end + (start - end) * progress_remaining
+
+        return (float(lin(self.learning_rate, self.learning_rate_end)), float(lin(self.clip_range, self.clip_range_end)),
+                -1.0 if self.clip_range_vf is None else float(self.clip_range_vf),
+                math.inf if self.target_kl is None else 1.5 * float(self.target_kl))
 
     @classmethod
     def gpu_defaults(cls, **over) -> "PPOConfig":
@@ -198,6 +230,75 @@ class D2DPPORollout(_C.Structure):
                                            "done_buf", "start0", "act_env", "adv_buf", "ret_buf", "stats")]
 
 
+class D2DPPOCtl(_C.Structure):
+    """include/d2d_ppo.h ``d2d_ppo_ctl``: the control block's eight words (``ControlBlock.buf[:8]``)."""
+    _fields_ = [(k, _C.c_float) for k in ("lr", "clip", "clip_vf", "kl_limit")] + \
+               [("stop", _C.c_int32), ("count", _C.c_int32), ("kl_sum", _C.c_float), ("kl_last", _C.c_float)]
+
+
+PPO_CTL_VERSION = 1
+_STAT_KEYS = ("policy_loss", "value_loss", "entropy", "clip_fraction")
+
+
+class ControlBlock:
+    """The device-resident control block of one update (include/d2d_ppo.h ``d2d_ppo_ctl``) and, behind
+    it in the same 12-float tensor, the four loss statistics, so one transfer brings everything an
+    update's record needs.  The host writes the coefficients (``set``: one stream-ordered copy, outside
+    any graph); the update's kernels -- or, on the torch paths, ``record`` / ``decide`` -- do the rest."""
+    WORDS = _C.sizeof(D2DPPOCtl) // 4
+    LR, CLIP, CLIP_VF, KL_LIMIT, STOP, COUNT, KL_SUM, KL_LAST = range(8)
+
+    def __init__(self, device):
+        self.buf = torch.zeros(self.WORDS + len(_STAT_KEYS), device=device)
+        self.ibuf = self.buf.view(torch.int32)
+        self.coef = None  # the host's copy of (lr, clip, clip_vf, kl_limit)
+        self.set(0.0, 0.0, -1.0, math.inf)
+
+    def ptr(self) -> int:
+        return self.buf.data_ptr()
+
+    def acc(self) -> dict:
+        return {k: self.buf[self.WORDS + i] for i, k in enumerate(_STAT_KEYS)}
+
+    def set(self, lr: float, clip: float, clip_vf: float, kl_limit: float):
+        host = torch.tensor([lr, clip, clip_vf, kl_limit], dtype=torch.float32)
+        self.coef = tuple(float(x) for x in (lr, clip, clip_vf, kl_limit))
+        self.buf[:4].copy_(host, non_blocking=True)
+
+    def read(self) -> dict:
+        """The update's record entries (one device-to-host copy): the four means over the recorded
+        minibatches, approx_kl, n_minibatches, early_stop and the coefficients the update used."""
+        h = self.buf.detach().cpu()
+        hi = h.view(torch.int32)
+        n = int(hi[self.COUNT])
+        out = {k: float(h[self.WORDS + i]) / max(n, 1) for i, k in enumerate(_STAT_KEYS)}
+        out.update(approx_kl=float(h[self.KL_SUM]) / max(n, 1), n_minibatches=n, early_stop=int(hi[self.STOP]),
+                   learning_rate=float(h[self.LR]), clip_range=float(h[self.CLIP]))
+        if float(h[self.CLIP_VF]) >= 0.0:
+            out["clip_range_vf"] = float(h[self.CLIP_VF])
+        return out
+
+    # the torch paths' halves of the *_ctl kernels (CPU ManualStep, autograd)
+    def reset(self):
+        self.buf[self.STOP:self.WORDS].zero_()
+
+    def stopped(self) -> bool:
+        return bool(self.ibuf[self.STOP])
+
+    def record(self, kl: torch.Tensor):
+        self.ibuf[self.COUNT] += 1
+        self.buf[self.KL_LAST] = kl
+        self.buf[self.KL_SUM] += kl
+
+    def decide(self) -> bool:
+        """SB3's check, after the statistics: True (and the stop flag set) when the last KL exceeds
+        the limit, so the caller must not step."""
+        if float(self.buf[self.KL_LAST]) > self.coef[3]:
+            self.ibuf[self.STOP] = 1
+            return True
+        return False
+
+
 def ppo_native():
     """ctypes binding of libd2d_ppo.so (include/d2d_ppo.h), loaded once; no fallback on a GPU."""
     global _PPO_LIB
@@ -232,12 +333,20 @@ def ppo_native():
             "d2d_ppo_fused_rows": [i32],
             "d2d_ppo_fused_grad": [i32, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, f32, vp, vp, i32, vp, vp, vp],
             "d2d_ppo_grad_reduce": [i32, i32, vp, vp, i32, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp],
+            # the control path (additive to ABI v6; versioned by d2d_ppo_ctl_version)
+            "d2d_ppo_ctl_version": [],
+            "d2d_ppo_ctl_reset": [vp, vp],
+            "d2d_ppo_fused_grad_ctl": [i32, vp, vp, vp, vp, vp, vp, vp, vp, vp, i32, f32, vp, vp, i32, vp, vp, vp, vp],
+            "d2d_ppo_grad_reduce_ctl": [i32, i32, vp, vp, i32, vp, i32, vp, f32, vp, vp, vp, vp, vp, vp, vp],
+            "d2d_ppo_adam_ctl": [i32, vp, vp, vp, vp, vp, f32, f32, f32, f32, vp, vp],
         }
         for name, args in sig.items():
             fn = getattr(lib, name)
             fn.restype, fn.argtypes = C.c_int32, args
         if lib.d2d_ppo_abi_version() != 6:
             raise RuntimeError("libd2d_ppo.so ABI mismatch")
+        if lib.d2d_ppo_ctl_version() != PPO_CTL_VERSION:
+            raise RuntimeError("libd2d_ppo.so control-block version mismatch")
         _PPO_LIB = lib
     return _PPO_LIB
 
@@ -275,14 +384,28 @@ class ManualStep:
         the gradient between the two equal branches, whose derivatives are then both adv_i)
       d logp / d mean = z / sigma, d logp / d log_std = z^2 - 1 (z = (a - mean) / sigma);
       entropy bonus: d(-ent_coef mean H) / d log_std = -ent_coef; value: vf_coef * -2 (R - V) / M.
-    Adam as torch.optim.Adam (lerp first moment, bias corrections, eps outside the square root)."""
+    Adam as torch.optim.Adam (lerp first moment, bias corrections, eps outside the square root).
+
+    With ``cfg.control`` the step takes its learning rate, clip range and value clip range from the
+    control block ``ctl`` (``set_coefs``), the rollout tuple has a sixth entry (the stored values),
+    ``grad`` also records approx_kl, and ``apply`` is SB3's target_kl check before the optimiser step:
+    once a minibatch's KL exceeds the limit neither it nor any later ``step`` of the update
+    (until ``reset_control``) changes anything.  On a GPU these are the ``*_ctl`` entry points of
+    libd2d_ppo.so, which read the block on the device, so the sequence captures into a HIP graph."""
 
     def __init__(self, policy: ActorCritic, cfg: PPOConfig, device):
         self.pol, self.cfg = policy, cfg
         params = list(policy.parameters())
         n = sum(p.numel() for p in params)
         self.P = torch.zeros(n, device=device)
-        self.G = torch.zeros(n, device=device)
+        self.ctl = ControlBlock(device) if cfg.control else None
+        if self.ctl is not None:
+            # one float behind G: the minibatch KL rides in the gradient's collective (apply, world > 1)
+            self.Gx = torch.zeros(n + 1, device=device)
+            self.G = self.Gx[:n]
+            self.set_coefs()
+        else:
+            self.G = torch.zeros(n, device=device)
         self.m = torch.zeros(n, device=device)
         self.v = torch.zeros(n, device=device)
         self.t = torch.zeros((), device=device)
@@ -294,6 +417,9 @@ class ManualStep:
         # D2D_PPO_FUSED=1 (default): forward + backward + weight gradients in one launch
         # (d2d_ppo_fused_grad) + the reduce; 0: the separate kernels (forward, backward, wgrad + reduce)
         self.fused = self.lib is not None and os.environ.get("D2D_PPO_FUSED", "1") == "1"
+        if self.ctl is not None and self.lib is not None and not self.fused:
+            raise RuntimeError("the PPO control path (learning_rate_end, clip_range_end, clip_range_vf, target_kl) "
+                               "has no separate-kernel variant: unset D2D_PPO_FUSED=0")
         o = 0
         for p in params:
             k = p.numel()
@@ -306,19 +432,34 @@ class ManualStep:
         self.grad(idx, rollout, acc, adv_ws)
         self.apply(world)
 
+    def set_coefs(self, progress_remaining: float = 1.0):
+        """Write this update's coefficients (``cfg.coefs``) into the control block."""
+        self.ctl.set(*self.cfg.coefs(progress_remaining))
+
+    def reset_control(self):
+        """The first step of an update: clear the stop flag, the count and the KL sums."""
+        if self.lib is not None:
+            _ok(self.lib.d2d_ppo_ctl_reset(self.ctl.ptr(), self._stream()), "d2d_ppo_ctl_reset")
+        else:
+            self.ctl.reset()
+
     def grad(self, idx, rollout, acc: dict, adv_ws=None):
         """The loss gradient of minibatch ``idx`` of ``rollout`` = (obs, actions, old log-probs,
-        advantages, returns) into ``G``; statistics added to ``acc``."""
+        advantages, returns[, old values: the control path]) into ``G``; statistics added to ``acc``."""
         cfg, pol = self.cfg, self.pol
         pn, vn = pol.mlp_extractor.policy_net, pol.mlp_extractor.value_net
         W1p, W2p, W1v, W2v = pn[0].weight, pn[2].weight, vn[0].weight, vn[2].weight
         W3p, W3v, ls = pol.action_net.weight, pol.value_net.weight, pol.log_std
-        obs_all, act_all, ol_all, adv_all, ret_all = rollout
+        if self.ctl is not None and len(rollout) < 6:
+            raise ValueError("the control path needs the rollout's stored values as rollout[5]")
+        obs_all, act_all, ol_all, adv_all, ret_all = rollout[:5]
         if self.lib is not None:
             if self.fused:
                 self._grad_fused(idx, rollout, acc, adv_ws)
             else:
-                self._grad_hip(idx, rollout, acc)
+                self._grad_hip(idx, rollout[:5], acc)
+            return
+        if self.ctl is not None and self.ctl.stopped():
             return
         X = obs_all[idx]
         M, c = X.shape[0], cfg.clip_range
@@ -329,7 +470,8 @@ class ManualStep:
         h1v = torch.tanh(torch.addmm(vn[0].bias, X, W1v.t()))
         h2v = torch.tanh(torch.addmm(vn[2].bias, h1v, W2v.t()))
         V = torch.addmm(pol.value_net.bias, h2v, W3v.t()).squeeze(1)
-        g_mean, g_V = self._head_torch(mean, V, act_all[idx], ol_all[idx], adv_all[idx], ret_all[idx], acc)
+        g_mean, g_V = self._head_torch(mean, V, act_all[idx], ol_all[idx], adv_all[idx], ret_all[idx], acc,
+                                       rollout[5][idx] if self.ctl is not None else None)
         tg = self._tanh_grad_torch
         # backward: the layer-output gradients, then every weight / bias gradient
         g2p = tg(h2p, torch.mm(g_mean, W3p))
@@ -396,14 +538,14 @@ class ManualStep:
         import ctypes as C
 
         cfg, pol, lib, st = self.cfg, self.pol, self.lib, self._stream()
-        obs_all, act_all, ol_all, adv_all, ret_all = rollout
+        obs_all, act_all, ol_all, adv_all, ret_all = rollout[:5]
         M, dev = idx.numel(), self.P.device
         key = ("fused", M)
         if key not in self._bufs:
             rows = lib.d2d_ppo_fused_rows(M)
             nb = (M + 63) // 64
             self._bufs[key] = {"rows": rows, "wpart": torch.empty(rows * self.G.numel(), device=dev),
-                               "hpart": torch.empty(2 * rows * 5, device=dev),
+                               "hpart": torch.empty(2 * rows * (5 if self.ctl is None else 6), device=dev),
                                "ws": torch.zeros(nb, 2, dtype=torch.float64, device=dev)}
         b = self._bufs[key]
         pn, vn = pol.mlp_extractor.policy_net, pol.mlp_extractor.value_net
@@ -418,11 +560,25 @@ class ManualStep:
         ws = adv_ws if adv_ws is not None else b["ws"].data_ptr()
         if norm and adv_ws is None:
             _ok(lib.d2d_ppo_adv_stats(M, idx.data_ptr(), adv_all.data_ptr(), ws, st), "d2d_ppo_adv_stats")
+        ls = pol.log_std
+        if self.ctl is not None:
+            # the control variants: clip / clip_vf / the stop flag from the block, KL into it
+            ov, ctl = rollout[5], self.ctl.ptr()
+            _ok(lib.d2d_ppo_fused_grad_ctl(M, idx.data_ptr(), obs_all.data_ptr(), act_all.data_ptr(), ol_all.data_ptr(),
+                                           adv_all.data_ptr(), ret_all.data_ptr(), ov.data_ptr(), ls.data_ptr(), ws,
+                                           norm, cfg.vf_coef, self.weight_ptrs(), offsets, self.G.numel(),
+                                           b["wpart"].data_ptr(), b["hpart"].data_ptr(), ctl, st),
+                "d2d_ppo_fused_grad_ctl")
+            _ok(lib.d2d_ppo_grad_reduce_ctl(b["rows"], self.G.numel(), b["wpart"].data_ptr(), base, 2 * b["rows"],
+                                            b["hpart"].data_ptr(), M, ls.data_ptr(), cfg.ent_coef, ls.grad.data_ptr(),
+                                            acc["policy_loss"].data_ptr(), acc["value_loss"].data_ptr(),
+                                            acc["entropy"].data_ptr(), acc["clip_fraction"].data_ptr(), ctl, st),
+                "d2d_ppo_grad_reduce_ctl")
+            return
         _ok(lib.d2d_ppo_fused_grad(M, idx.data_ptr(), obs_all.data_ptr(), act_all.data_ptr(), ol_all.data_ptr(),
                                    adv_all.data_ptr(), ret_all.data_ptr(), pol.log_std.data_ptr(), ws,
                                    norm, cfg.clip_range, cfg.vf_coef, self.weight_ptrs(), offsets, self.G.numel(),
                                    b["wpart"].data_ptr(), b["hpart"].data_ptr(), st), "d2d_ppo_fused_grad")
-        ls = pol.log_std
         _ok(lib.d2d_ppo_grad_reduce(b["rows"], self.G.numel(), b["wpart"].data_ptr(), base, 2 * b["rows"],
                                     b["hpart"].data_ptr(), M, ls.data_ptr(), cfg.ent_coef, ls.grad.data_ptr(),
                                     acc["policy_loss"].data_ptr(), acc["value_loss"].data_ptr(),
@@ -474,9 +630,12 @@ class ManualStep:
     def _stream(self):
         return torch.cuda.current_stream(self.P.device).cuda_stream
 
-    def _head_torch(self, mean, V, A, OL, ADV, R, acc):
+    def _head_torch(self, mean, V, A, OL, ADV, R, acc, OV=None):
         cfg, ls = self.cfg, self.pol.log_std
         M, c = mean.shape[0], cfg.clip_range
+        cv = -1.0
+        if self.ctl is not None:
+            c, cv = self.ctl.coef[1], self.ctl.coef[2]
         isig = torch.exp(-ls)
         z = (A - mean) * isig
         logp = (-0.5 * z * z - ls - _HALF_LOG_2PI).sum(1)
@@ -493,18 +652,45 @@ class ManualStep:
         gz = g_lp[:, None] * z
         g_mean = gz * isig
         g_V = err * (-2.0 * cfg.vf_coef / M)
+        if cv >= 0.0:
+            # SB3 clip_range_vf: the prediction clipped around the stored value; torch.clamp's gradient
+            # passes on the closed interval
+            d = V - OV
+            err = R - (OV + torch.clamp(d, -cv, cv))
+            vl = (err * err).mean()
+            g_V = torch.where(d.abs() <= cv, err * (-2.0 * cfg.vf_coef / M), 0.0)
         torch.sum(gz * z - g_lp[:, None], 0, out=ls.grad)
         ls.grad.sub_(cfg.ent_coef)
         acc["policy_loss"] += pl
         acc["value_loss"] += vl
         acc["entropy"] += (0.5 + _HALF_LOG_2PI + ls).sum()
         acc["clip_fraction"] += ((ratio - 1).abs() > c).float().mean()
+        if self.ctl is not None:
+            self.ctl.record(((ratio - 1) - (logp - OL)).mean())
         return g_mean, g_V
 
     def apply(self, world: int = 1):
-        """Rank-mean of ``G`` (RCCL), clip_grad_norm_, Adam step on ``P``."""
+        """Rank-mean of ``G`` (RCCL), clip_grad_norm_, Adam step on ``P``.  Control path: SB3's
+        target_kl check first, on the rank mean of the minibatch KL, which travels behind ``G`` in the
+        same collective so that every rank takes the same decision."""
         cfg, G = self.cfg, self.G
-        if world > 1:
+        lr = cfg.learning_rate
+        if self.ctl is not None:
+            kl_last = self.ctl.buf[ControlBlock.KL_LAST:ControlBlock.KL_LAST + 1]
+            if world > 1:
+                self.Gx[-1:].copy_(kl_last)
+                dist.all_reduce(self.Gx)
+                self.Gx.div_(world)
+                kl_last.copy_(self.Gx[-1:])
+            if self.lib is not None:
+                _ok(self.lib.d2d_ppo_adam_ctl(G.numel(), self.P.data_ptr(), G.data_ptr(), self.m.data_ptr(),
+                                              self.v.data_ptr(), self.t.data_ptr(), 0.9, 0.999, 1e-5,
+                                              cfg.max_grad_norm, self.ctl.ptr(), self._stream()), "d2d_ppo_adam_ctl")
+                return
+            if self.ctl.stopped() or self.ctl.decide():
+                return
+            lr = self.ctl.coef[0]
+        elif world > 1:
             dist.all_reduce(G)  # data-parallel PPO: mean gradient over the ranks (RCCL)
             G.div_(world)
         if self.lib is not None:
@@ -521,7 +707,7 @@ class ManualStep:
         self.v.mul_(b2).addcmul_(G, G, value=1.0 - b2)
         bc1 = 1.0 - torch.pow(b1, self.t)
         bc2s = torch.sqrt(1.0 - torch.pow(b2, self.t))
-        self.P.sub_(self.m * (cfg.learning_rate / bc1) / (self.v.sqrt() / bc2s + eps))
+        self.P.sub_(self.m * (lr / bc1) / (self.v.sqrt() / bc2s + eps))
 
 
 def compute_gae(rewards, values, episode_starts, last_values, last_dones, gamma, gae_lambda):
@@ -576,6 +762,14 @@ class PPO:
         z = torch.zeros((), device=dev)
         self._acc = {"policy_loss": z.clone(), "value_loss": z.clone(), "entropy": z.clone(),
                      "clip_fraction": z.clone()}
+        # PPO control: SB3's progress_remaining (learn() sets it after every rollout; a caller of train()
+        # may set it), and the control block -- ManualStep's, or one of this object's for the autograd
+        # path -- whose tail holds the statistics, so an update's record is one transfer
+        self.progress_remaining = 1.0
+        self._ctl = None
+        if self.cfg.control:
+            self._ctl = self.manual.ctl if self.manual is not None else ControlBlock(dev)
+            self._acc = self._ctl.acc()
         self._graph = None
         self._gidx = None
         self._ro = None          # rollout buffers (_alloc_rollout)
@@ -807,7 +1001,10 @@ class PPO:
         obs, act, old_logp, adv_all, ret = self._flat
         if self.manual is not None:
             with torch.no_grad():
-                self.manual.step(idx, self._flat, self._acc, self.world, adv_ws)
+                self.manual.step(idx, self._rollout_data(), self._acc, self.world, adv_ws)
+            return
+        if self._ctl is not None:
+            self._minibatch_control(idx)
             return
         c = self.cfg.clip_range
         params = list(self.policy.parameters())
@@ -841,6 +1038,61 @@ class PPO:
             self._acc["entropy"] -= el
             self._acc["clip_fraction"] += ((ratio - 1).abs() > c).float().mean()
 
+    def _rollout_data(self) -> tuple:
+        """ManualStep's rollout tuple; on the control path with the rollout's stored values (SB3's
+        ``old_values``: the buffer the rollout wrote, in the flat buffers' sample order)."""
+        if self._ctl is None:
+            return self._flat
+        return self._flat + (self._ro["val"].reshape(-1),)
+
+    def _minibatch_control(self, idx: torch.Tensor):
+        """``_minibatch``'s autograd branch on the control path, in SB3 ``PPO.train``'s order: loss (with
+        ``clip_range_vf``), statistics, approx_kl, the target_kl check, and only then the step.  The
+        backward pass runs before the check, so that a multi-rank run can send the KL behind the
+        gradients in their one collective; a stopped minibatch's gradients are simply not applied."""
+        ctl = self._ctl
+        if ctl.stopped():
+            return
+        _, c, cv, _ = ctl.coef
+        obs, act, old_logp, adv_all, ret = self._flat
+        params = list(self.policy.parameters())
+        values, logp, entropy = self.policy.evaluate_actions(obs[idx], act[idx])
+        adv = adv_all[idx]
+        if self.cfg.normalize_advantage and idx.numel() > 1:
+            adv = (adv - adv.mean()) / (adv.std() + 1e-8)
+        log_ratio = logp - old_logp[idx]
+        ratio = torch.exp(log_ratio)
+        pl = -torch.min(adv * ratio, adv * torch.clamp(ratio, 1 - c, 1 + c)).mean()
+        if cv >= 0.0:
+            ov = self._ro["val"].reshape(-1)[idx]
+            values = ov + torch.clamp(values - ov, -cv, cv)
+        vl = torch.nn.functional.mse_loss(ret[idx], values)
+        el = -entropy.mean()
+        loss = pl + self.cfg.ent_coef * el + self.cfg.vf_coef * vl
+        self.opt.zero_grad(set_to_none=False)
+        loss.backward()
+        with torch.no_grad():
+            self._acc["policy_loss"] += pl
+            self._acc["value_loss"] += vl
+            self._acc["entropy"] -= el
+            self._acc["clip_fraction"] += ((ratio - 1).abs() > c).float().mean()
+            ctl.record(((ratio - 1) - log_ratio).mean())
+            if self.world > 1:
+                kl_last = ctl.buf[ControlBlock.KL_LAST:ControlBlock.KL_LAST + 1]
+                flat = torch.cat([p.grad.reshape(-1) for p in params] + [kl_last])
+                dist.all_reduce(flat)
+                flat /= self.world
+                o = 0
+                for p in params:
+                    k = p.numel()
+                    p.grad.copy_(flat[o:o + k].view_as(p))
+                    o += k
+                kl_last.copy_(flat[o:])
+        if ctl.decide():
+            return
+        torch.nn.utils.clip_grad_norm_(params, self.cfg.max_grad_norm)
+        self.opt.step()
+
     def _capture(self):
         """Record one full-size minibatch step as a HIP graph: forward, backward, grad clipping and
         the (capturable) Adam step replay with no per-kernel launches from Python."""
@@ -861,6 +1113,8 @@ class PPO:
         (d2d_ppo_permute), then every minibatch step; nothing waits for the host, so on one rank the
         whole update is captured and replayed as one HIP graph."""
         M, bs, E = self._flat[0].shape[0], self.cfg.batch_size, self.cfg.n_epochs
+        if self._ctl is not None:
+            self.manual.reset_control()  # the update's first node
         for v in self._acc.values():
             v.zero_()
         lib, st = self.manual.lib, self.manual._stream()
@@ -883,7 +1137,18 @@ class PPO:
                 self._minibatch(self._perm[e * M + s:e * M + s + n], adv_ws=aw)
 
     def train(self) -> dict:
+        """One update on the last rollout.  On the control path (``cfg.control``) the coefficients of
+        ``cfg.coefs(self.progress_remaining)`` are written to the control block first -- one small copy,
+        outside the captured graph, which reads them from memory on every replay -- and the record
+        gains ``approx_kl``, ``n_minibatches``, ``early_stop``, ``learning_rate``, ``clip_range`` and
+        (when on) ``clip_range_vf``; the four means are over the recorded minibatches."""
         M, bs = self._flat[0].shape[0], self.cfg.batch_size
+        ctl = self._ctl
+        if ctl is not None:
+            ctl.set(*self.cfg.coefs(self.progress_remaining))
+            if self.opt is not None:
+                for grp in self.opt.param_groups:
+                    grp["lr"] = ctl.coef[0]
         if self._hip:
             if self._perm is None:
                 self._perm = torch.empty(self.cfg.n_epochs * M, dtype=torch.int64, device=self.device)
@@ -900,17 +1165,25 @@ class PPO:
             else:
                 self._train_body_hip()
                 self._upd_warm = True
+            if ctl is not None:
+                return ctl.read()  # the statistics and the counters in one transfer
             n_upd = self.cfg.n_epochs * -(-M // bs)
             return {k: float(v) / n_upd for k, v in self._acc.items()}
+        if ctl is not None:
+            ctl.reset()
         for v in self._acc.values():
             v.zero_()
         n_upd = 0
         warm = 0
         for _ in range(self.cfg.n_epochs):
+            # (a stopped update still draws every epoch's shuffle: the generator's state after an
+            # update does not depend on whether it stopped)
             perm = torch.randperm(M, device=self.device, generator=self.gen)
             for s in range(0, M, bs):
+                if ctl is not None and ctl.stopped():
+                    break
                 idx = perm[s:s + bs]
-                if self.use_graph and idx.numel() == bs:
+                if self.use_graph and idx.numel() == bs and ctl is None:
                     if self._graph is None and warm >= 3:
                         # capture after a few eager steps (lazy optimiser state, allocator warm-up)
                         torch.cuda.synchronize(self.device)
@@ -923,16 +1196,23 @@ class PPO:
                     warm += 1
                 self._minibatch(idx)
                 n_upd += 1
+        if ctl is not None:
+            return ctl.read()
         return {k: float(v) / max(n_upd, 1) for k, v in self._acc.items()}
 
     def learn(self, total_timesteps: int, log=None, checkpoint: Checkpoint | None = None, monitor=None,
-              logger=None) -> list[dict]:
+              logger=None, schedule_timesteps: int | None = None) -> list[dict]:
         """Alternate rollouts and updates until ``total_timesteps`` env steps (this rank);
         ``checkpoint``: save the agent whenever ``num_timesteps`` crosses a multiple of its
         ``save_freq`` (after the update, so a resumed run continues with the next rollout).
         ``monitor``: ``True`` or an ``EpisodeMonitor`` -- ``set_monitor`` it first (``None``: leave
         things as they are; off unless one was set).  ``logger``: a ``trainlog.ScalarLog`` (anything
-        with ``log(record)``) that gets every record after ``log``."""
+        with ``log(record)``) that gets every record after ``log``.  After each rollout and before its
+        update, ``progress_remaining = 1 - num_timesteps / total_timesteps`` (SB3's
+        ``OnPolicyAlgorithm.learn``; not below 0 when the last rollout overshoots), which the schedules
+        ``learning_rate_end`` / ``clip_range_end`` read; ``schedule_timesteps``: the schedule's horizon
+        when it is not this call's ``total_timesteps`` (a run driven by several ``learn`` calls)."""
+        horizon = float(schedule_timesteps if schedule_timesteps is not None else total_timesteps)
         if monitor is not None:
             self.set_monitor(monitor)
         hist = []
@@ -943,6 +1223,7 @@ class PPO:
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)
             t1 = time.perf_counter()
+            self.progress_remaining = max(0.0, 1.0 - self.num_timesteps / horizon)
             tr = self.train()
             if self.device.type == "cuda":
                 torch.cuda.synchronize(self.device)

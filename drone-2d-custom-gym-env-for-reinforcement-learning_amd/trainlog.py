@@ -86,7 +86,9 @@ def encode_event(wall_time: float, step: int, scalars: dict | None = None, file_
     return ev
 
 
-_TRAIN_KEYS = ("policy_loss", "value_loss", "entropy", "clip_fraction")
+# the last six are in a record only when the PPO control path is on (PPOConfig.control)
+_TRAIN_KEYS = ("policy_loss", "value_loss", "entropy", "clip_fraction", "approx_kl", "n_minibatches", "early_stop",
+               "learning_rate", "clip_range", "clip_range_vf")
 
 
 def record_scalars(rec: dict, total_episodes: float | None = None) -> dict:

@@ -17,7 +17,10 @@
 extern "C" {
 #endif
 
-#define D2D_PPO_ABI_VERSION 6  /* v6 (round 4): d2d_ppo_adam_spread / d2d_ppo_wgrad_head_adam removed */
+#define D2D_PPO_ABI_VERSION 6  /* v6 (round 4): d2d_ppo_adam_spread / d2d_ppo_wgrad_head_adam removed.  The control
+                                  entry points below (d2d_ppo_ctl_*, *_ctl) are additive: every v6 function keeps
+                                  its signature and behaviour, so the version stays; the control block has a
+                                  version of its own (D2D_PPO_CTL_VERSION) */
 #define D2D_PPO_HEAD_BLOCK 64  /* v1: 256 */
 
 int32_t d2d_ppo_abi_version(void);
@@ -119,6 +122,85 @@ int32_t d2d_ppo_grad_reduce(int32_t n_rows, int32_t row_len, const float* partia
                             const float* head_partial, int32_t m, const float* log_std, float ent_coef,
                             float* log_std_grad, float* acc_pl, float* acc_vl, float* acc_ent, float* acc_clip,
                             void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * PPO control: schedules, value clipping, approx_kl and SB3's target_kl stop inside a captured update.
+ *
+ * The by-value coefficients of the entry points above are frozen when an update is captured into a
+ * HIP graph, and nothing in a replayed update can wait for the host.  The *_ctl entry points read
+ * their coefficients from, and leave their decisions in, one small block of device memory instead:
+ * the host writes the first four words before each update (one stream-ordered copy outside the
+ * graph) and reads the block back with the update's statistics.  Layout (8 x 4 bytes; mirrored by
+ * drone2d_amd.ppo.D2DPPOCtl):
+ *
+ *   word 0  float   lr        learning rate of this update
+ *   word 1  float   clip      clip_range of this update
+ *   word 2  float   clip_vf   clip_range_vf; negative: value clipping off
+ *   word 3  float   kl_limit  1.5 * target_kl, or +inf (never stop)
+ *   word 4  int32   stop      set by d2d_ppo_adam_ctl when a minibatch's KL exceeds kl_limit
+ *   word 5  int32   count     minibatches whose statistics were recorded (the stopping one included)
+ *   word 6  float   kl_sum    sum of the recorded minibatches' approx_kl, in launch order
+ *   word 7  float   kl_last   approx_kl of the last recorded minibatch
+ *
+ * One update is: d2d_ppo_ctl_reset, then per minibatch d2d_ppo_fused_grad_ctl, d2d_ppo_grad_reduce_ctl,
+ * (multi-rank: the collective over g and kl_last,) d2d_ppo_adam_ctl.  SB3's order (PPO.train): the
+ * minibatch's statistics are recorded, approx_kl = mean((ratio - 1) - log_ratio) is computed, and if
+ * it exceeds kl_limit that minibatch's optimiser step is not taken and the rest of the update is
+ * skipped.  Once `stop` is set, every later *_ctl launch of the update returns at once (the fused
+ * gradient before its first barrier: the flag is uniform over the grid), so a stopped update still
+ * executes its launches, as near-empty ones.  The shuffles (d2d_ppo_permute) and the up-front
+ * advantage statistics are not part of the control path: a stopped update has drawn all its n_epochs
+ * shuffles and advanced the shuffle counter by n_epochs, so a run is reproducible whether or not an
+ * update stopped.
+ *
+ * The decision sits in d2d_ppo_adam_ctl, not in the reduce, so that a multi-rank run can replace
+ * kl_last by its rank mean between the two (every rank must take the same decision).
+ *
+ * Only the fused path (d2d_ppo_fused_grad) has control variants.  The separate kernels
+ * (d2d_ppo_mlp_forward_adv / d2d_ppo_mlp_backward / d2d_ppo_wgrad_head, D2D_PPO_FUSED=0) are a
+ * diagnostic A/B path; drone2d_amd.ppo.ManualStep refuses the control path there with an error. */
+#define D2D_PPO_CTL_VERSION 1
+typedef struct d2d_ppo_ctl {
+    float lr;
+    float clip;
+    float clip_vf;
+    float kl_limit;
+    int32_t stop;
+    int32_t count;
+    float kl_sum;
+    float kl_last;
+} d2d_ppo_ctl;
+int32_t d2d_ppo_ctl_version(void);
+
+/* The first launch of an update: stop = 0, count = 0, kl_sum = 0, kl_last = 0 (the coefficients stay). */
+int32_t d2d_ppo_ctl_reset(d2d_ppo_ctl* ctl, void* stream);
+
+/* d2d_ppo_fused_grad (the same kernel, instantiated a second time) with clip and clip_vf read from
+ * ctl.  old_values [rollout rows]: the rollout's stored value predictions (SB3 rollout_data.old_values,
+ * not returns - advantages, which rounds differently); with clip_vf >= 0 the value head uses
+ * values_pred = old + clamp(value - old, -clip_vf, clip_vf), value loss mean((ret - values_pred)^2),
+ * whose gradient passes where |value - old| <= clip_vf (bounds included) and is zero elsewhere.  The
+ * policy head's row of hpart has a sixth sum, sum((ratio - 1) - log_ratio): hpart is [2 R][6] here.
+ * Returns without writing anything when ctl->stop is set. */
+int32_t d2d_ppo_fused_grad_ctl(int32_t m, const int64_t* idx, const float* obs, const float* act,
+                               const float* old_logp, const float* adv, const float* ret, const float* old_values,
+                               const float* log_std, const double* ws, int32_t normalize, float vf_coef,
+                               const float* const* weights, const int32_t* offsets, int32_t row_len, float* wpart,
+                               float* hpart, const d2d_ppo_ctl* ctl, void* stream);
+
+/* d2d_ppo_grad_reduce over the [n_blocks][6] head rows.  Nothing when ctl->stop is set; otherwise g,
+ * log_std's gradient and the four statistics as d2d_ppo_grad_reduce, then (one thread, plain stores,
+ * fixed order) count += 1, kl_last = the minibatch's approx_kl, kl_sum += kl_last. */
+int32_t d2d_ppo_grad_reduce_ctl(int32_t n_rows, int32_t row_len, const float* partial, float* g, int32_t n_blocks,
+                                const float* head_partial, int32_t m, const float* log_std, float ent_coef,
+                                float* log_std_grad, float* acc_pl, float* acc_vl, float* acc_ent, float* acc_clip,
+                                d2d_ppo_ctl* ctl, void* stream);
+
+/* d2d_ppo_adam with lr read from ctl.  Nothing when ctl->stop is set; when kl_last > kl_limit one
+ * thread sets stop and no thread steps (p, g, m1, m2 and *t stay as they are); otherwise
+ * d2d_ppo_adam's step. */
+int32_t d2d_ppo_adam_ctl(int32_t n, float* p, float* g, float* m1, float* m2, float* t, float b1, float b2, float eps,
+                         float max_norm, d2d_ppo_ctl* ctl, void* stream);
 
 typedef struct d2d_ppo_rollout {
     int32_t n;            /* envs */
