@@ -651,11 +651,11 @@ __device__ __forceinline__ void brent_step(const S& s, const PathK& K, double px
 // its entry num + it; entry nums are at most BT_K + 1 (a golden-march snapshot), so num < 500 holds
 // for every active lane while it + BT_K + 1 < 500 and the per-lane count is only tested past that
 // (never reached by a search over a finite bracket: the golden steps alone shrink it below xtol in
-// ~60 passes).  brent_step does not advance num; B.num stays the entry count.
+// ~60 passes).  brent_step does not advance num; B.num stays the entry count.  (IT_FREE: a caller
+// whose entry nums are larger passes 500 - their bound, bt_finish_join.)
 template <bool KN = false, class S>
 __device__ __forceinline__ void brent_run(const S& s, const PathK& K, double px, double py, Brent& B,
-                                          double* kn = nullptr) {
-    constexpr int IT_FREE = 500 - (BT_K_MAX + 1);
+                                          double* kn = nullptr, const int IT_FREE = 500 - (BT_K_MAX + 1)) {
     for (int it = 0;; ++it) {
         bool act = brent_open(B);
         if (__builtin_expect(it >= IT_FREE, 0)) {
@@ -902,13 +902,8 @@ __device__ __forceinline__ void bt_verify(const BtHot* hot, BtLane& L, int k0, i
     L.fb = fb;
     L.fc = fc;
 }
-// resume brent_step from the snapshot before step dev (a search that followed the table restores
-// its final state, which is inactive unless the march is longer than BT_K); iu = result's interval
-template <bool LT, class SC>
-__device__ __forceinline__ double bt_finish(const SC& s, const BrTab& T, const BtHot* hot, int kind, int dev,
-                                            double px, double py, int& iu) {
-    const BtSnap& S = T.snap[kind][dev];
-    Brent B;
+// the search state before step k of a kind's march (BtSnap), and its three distances for this point
+__device__ __forceinline__ void bt_restore(const BtSnap& S, Brent& B) {
     B.a = S.a;
     B.b = S.b;
     B.fulc = S.fulc;
@@ -922,11 +917,25 @@ __device__ __forceinline__ double bt_finish(const SC& s, const BrTab& T, const B
     B.ia = S.ia;
     B.ib = S.ib;
     B.ixf = S.ixf;
+}
+template <bool LT>
+__device__ __forceinline__ void bt_restore_f(const BtSnap& S, const BtHot* hot, int kind, double px, double py,
+                                             Brent& B) {
+    B.ffulc = bt_dist<LT>(hot, kind, S.j_fulc, px, py);
+    B.fnfc = bt_dist<LT>(hot, kind, S.j_nfc, px, py);
+    B.fx = bt_dist<LT>(hot, kind, S.j_xf, px, py);
+}
+// resume brent_step from the snapshot before step dev (a search that followed the table restores
+// its final state, which is inactive unless the march is longer than BT_K); iu = result's interval
+template <bool LT, class SC>
+__device__ __forceinline__ double bt_finish(const SC& s, const BrTab& T, const BtHot* hot, int kind, int dev,
+                                            double px, double py, int& iu) {
+    const BtSnap& S = T.snap[kind][dev];
+    Brent B;
+    bt_restore(S, B);
     if (__ballot(brent_active(B)) != 0ull) {
         const PathK K = path_k(s);
-        B.ffulc = bt_dist<LT>(hot, kind, S.j_fulc, px, py);
-        B.fnfc = bt_dist<LT>(hot, kind, S.j_nfc, px, py);
-        B.fx = bt_dist<LT>(hot, kind, S.j_xf, px, py);
+        bt_restore_f<LT>(S, hot, kind, px, py, B);
         brent_run(s, K, px, py, B);
     }
     iu = B.ixf;
@@ -942,6 +951,22 @@ __device__ __forceinline__ double closest_u_tab(const S& s, const BrTab& T, cons
 // split point of the two-wave re-check: the first wave checks steps [1, bt_split), the second
 // [bt_split, len) (from its own window, bt_window)
 __device__ __forceinline__ int bt_split(const BrTab& T) { return max(4, (T.len[0] + 3) / 2); }
+// Early start (K1 at full load, bt_finish_join in d2d_kernels.h): the path wave re-checks steps
+// [1, BT_EARLY) only and resumes the lanes that deviate there at once, without waiting for the other
+// wave, which re-checks [BT_EARLY, len); the few lanes that deviate there join afterwards.  A multiple
+// of 3 plus 1, so the path wave's 3-step passes stay whole; 0: the split by halves above.
+// Measured at 65 536 corridor envs, us per step: 0 26.29, 7 29.57, 10 28.74, 13 26.75, 16 25.91 (kept),
+// 19 25.97, 22 26.16, 25 26.40, 28 26.60 (DESIGN.md "Where each lever stands").
+#ifndef D2D_BT_EARLY
+#define D2D_BT_EARLY 16
+#endif
+constexpr int BT_EARLY = D2D_BT_EARLY;
+// ... not in the grouped kernel, which shares k1_body: mixed 39.64 us with it against 39.17 / 39.03
+// without (parent / this build)
+#ifndef D2D_BT_EARLY_GRP
+#define D2D_BT_EARLY_GRP 0
+#endif
+static_assert(BT_EARLY == 0 || (BT_EARLY >= 4 && BT_EARLY % 3 == 1 && BT_EARLY < BT_K), "BT_EARLY");
 // three-way split: part p in {0, 1, 2} checks steps [bt_third(p), bt_third(p + 1)) (bt_third(0) = 1,
 // bt_third(3) = BT_K), as the fill kernel splits it
 __device__ __forceinline__ int bt_third(const BrTab& T, int p) {

@@ -12,9 +12,10 @@
 //       store the state; velocity part of the observation (obs 0-2, 17-18) and of the reward
 //   W1  sensor part (obs 3..16, CA inputs); for envs that end: the spawn-state sensor part
 //   W2  path role: Brent closest point through the golden-march tables (steps [1, bt_split) of the
-//       table re-check), obs 19..26, the position / path terms of the reward while the physics wave
-//       finishes (W0 takes the sum)
-//   W3  steps [bt_split, len) of W2's table re-check; then, for envs that end, the
+//       table re-check; at full load [1, BT_EARLY), its deviating lanes resumed at once: the early
+//       start, bt_finish_join), obs 19..26, the position / path terms of the reward while the physics
+//       wave finishes (W0 takes the sum)
+//   W3  steps [bt_split, len) ([BT_EARLY, len)) of W2's table re-check; then, for envs that end, the
 //       spawn state and the spawn-state path part
 //   (W1 and W3 take the spawn-state parts from the auto-reset observation cache when it is ready)
 //   epilogue (no barrier: an LDS count of the waves whose rows are written): W1-W3 store the 64x27
@@ -277,7 +278,9 @@ __device__ __forceinline__ int next_scenario(const StepArgs& a, int j, uint32_t 
 //   f_gs    W0 -> W1,W2,W3  joint sweep finished: the jb region becomes the obs tile
 //   f_rp    W2 -> W0        the position / path terms of the reward (W0 sums the reward: the physics
 //                           wave ends last at full load, so the sum waits for no other wave)
-//   f_ver   W3 -> W2        first differing step in the second half of the table re-check
+//   f_ver   W3 -> W2        first differing step in W3's part of the table re-check (early start: W2
+//                           polls it from its continuation loop and blocks only once that is dry;
+//                           W3's re-check depends on nothing of W2's)
 //   f_acc   W3 -> W0        the finished episodes' accumulators and the running path error / return
 //                           are in LDS (W0's epilogue)
 //   n_tile  W0..W3 -> W1..W3  count of waves whose obs-tile rows are written: W1-W3 store the tile
@@ -288,7 +291,7 @@ struct K1Shared {
     int scn[EPB];             // scenario index per env
     uint8_t cause[EPB];       // W0 -> W1, W2, W3: end cause (0: the env keeps running)
     uint8_t cvalid[EPB];      // W0 -> W1, W3: the env's reset-cache entry is ready
-    uint32_t pflags[EPB];     // W3 -> W2: first differing step of the second half of the table re-check;
+    uint32_t pflags[EPB];     // W3 -> W2: first differing step of W3's part of the table re-check;
                               // then W2 -> W0: LA-lock bit after the path role
     uint32_t ep[EPB];         // W0 -> W1, W3: episode counter (the state's copy changes at a reset)
     double sina[EPB];         // W0 -> W2: sin of the post-step frame angle (AA reward)
@@ -331,6 +334,57 @@ __device__ __forceinline__ void tile_arrive(uint32_t& c) {
 __device__ __forceinline__ void tile_wait(const uint32_t& c, uint32_t n) {
     while (__builtin_amdgcn_readfirstlane(*(const volatile LdsU32*)&c) < n) __builtin_amdgcn_s_sleep(1);
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup");
+}
+
+// bt_finish for the early start (BT_EARLY): the wave has re-checked steps [1, BT_EARLY) itself (L);
+// another wave re-checks [BT_EARLY, len), publishes each lane's first differing step in `dv` (len:
+// none) and raises `fv`.  Lanes that deviate in the wave's own part resume at once, in a loop of
+// brent_run's shape that also ends, for the whole wave, in the pass after the one whose read of the
+// flag saw it up (the LDS read is issued before the step and tested at the top of the next pass, so
+// its latency is off the chain).  Then -- after a wait for the flag when the loop ran dry first,
+// which includes a wave with no early deviator -- the lanes that deviate in the other wave's part
+// are restored from their snapshots and every lane that is still open runs brent_run together.
+// Every lane takes exactly the steps bt_finish takes from the same snapshot, so the result does not
+// depend on when the join happens.
+// scipy's evaluation count stays exact per lane: the first loop is capped at IT_JOIN passes (no lane
+// can reach 500 in it: an entry num is at most BT_K + 1), a lane carries its passes into brent_run
+// in num, and brent_run tests the count from the pass at which a lane could first reach 500.
+template <bool LT, class SC>
+__device__ __forceinline__ double bt_finish_join(const SC& s, const BrTab& T, const BtHot* hot, const BtLane& L,
+                                                 const uint32_t& fv, const uint32_t& dv, double px, double py,
+                                                 int& iu) {
+    constexpr int IT_JOIN = 200;
+    const PathK K = path_k(s);
+    const bool early = L.dev < L.len;
+    // one restore for every lane: the snapshot before its first differing step, or the table's last
+    // (L.dev == len: the lane followed the wave's part; what a lane that follows the whole table keeps)
+    Brent B;
+    bt_restore(T.snap[L.kind][L.dev], B);
+    if (__ballot(early) != 0ull) {
+        if (early) bt_restore_f<LT>(T.snap[L.kind][L.dev], hot, L.kind, px, py, B);
+        uint32_t up = 0u;  // the flag as the previous pass read it
+        int it = 0;
+        for (;; ++it) {
+            if (!(early & brent_open(B) & (it < IT_JOIN) & (__builtin_amdgcn_readfirstlane(up) == 0u))) break;
+            up = *(const volatile LdsU32*)&fv;
+            brent_step(s, K, px, py, B);
+        }
+        B.num += it;
+    }
+    flag_wait(fv);
+    // the join: lanes that deviate in the other wave's part (rare), or whose table ends open (a march
+    // longer than BT_K), start from their snapshot; wave-uniformly skipped when there is none
+    const bool late = !early & ((dv < (uint32_t)L.len) | brent_active(B));
+    if (__ballot(late) != 0ull) {
+        if (late) {
+            const BtSnap& S = T.snap[L.kind][min((uint32_t)L.len, dv)];
+            bt_restore(S, B);
+            bt_restore_f<LT>(S, hot, L.kind, px, py, B);
+        }
+    }
+    if (__ballot(brent_active(B)) != 0ull) brent_run(s, K, px, py, B, nullptr, 500 - (BT_K_MAX + 1) - IT_JOIN);
+    iu = B.ixf;
+    return B.xf;
 }
 
 // Scenario staging of a 256-thread K1 workgroup (group wg).  LDS: scenario tables in LDS; LTAB: the
@@ -378,6 +432,8 @@ __device__ __forceinline__ void k1_body(const StepArgs& a, const SC* scns, const
     const bool valid = gvalid && (GRP ? ie >= 0 : i < a.n);
     const int n = a.ns;
     const bool auto_reset = a.cfg.auto_reset != 0;
+    // the early start of W2's continuation (bt_finish_join): the full-load kernels with staged tables
+    constexpr bool EARLY = LDS && LTAB && !S3 && BT_EARLY > 0 && (!GRP || D2D_BT_EARLY_GRP);
     STAMP(0);
     if (wg == 0 && qt == 0 && a.fill_ctl)  // K4's tick: publish its next value
         __hip_atomic_store(&a.fill_ctl[0], __hip_atomic_load(&a.fill_ctl[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT),
@@ -658,12 +714,20 @@ __device__ __forceinline__ void k1_body(const StepArgs& a, const SC* scns, const
                 const BtHot* hot = LTAB ? hots + sh.scn[lane] : &T->hot;
                 BtLane L = bt_start<LTAB>(*T, hot, F.px, F.py);
                 // (tables in global memory: W2 re-checks the whole table, W3 none)
-                bt_verify<LTAB>(hot, L, 1, !LDS ? BT_K : S3 ? bt_third(*T, 1) : bt_split(*T), F.px, F.py);
-                flag_wait(sh.f_ver);
-                if (S3) flag_wait(sh.f_ver1);
-                L.dev = min(L.dev, (int)sh.pflags[lane]);
                 int iu;
-                const double u = bt_finish<LTAB>(S, *T, hot, L.kind, L.dev, F.px, F.py, iu);
+                double u;
+                if constexpr (EARLY) {
+                    // early start: steps [1, BT_EARLY) only, then the continuation at once; the lanes
+                    // that deviate in W3's part [BT_EARLY, len) join it later (bt_finish_join)
+                    bt_verify<LTAB>(hot, L, 1, BT_EARLY, F.px, F.py);
+                    u = bt_finish_join<LTAB>(S, *T, hot, L, sh.f_ver, sh.pflags[lane], F.px, F.py, iu);
+                } else {
+                    bt_verify<LTAB>(hot, L, 1, !LDS ? BT_K : S3 ? bt_third(*T, 1) : bt_split(*T), F.px, F.py);
+                    flag_wait(sh.f_ver);
+                    if (S3) flag_wait(sh.f_ver1);
+                    L.dev = min(L.dev, (int)sh.pflags[lane]);
+                    u = bt_finish<LTAB>(S, *T, hot, L.kind, L.dev, F.px, F.py, iu);
+                }
                 path_obs_u(a.cfg, S, F.px, F.py, F.a, u, f, po, iu);
             } else {
                 // (global-memory tables: the plain search scans the lane's knots staged in LDS)
@@ -719,13 +783,13 @@ __device__ __forceinline__ void k1_body(const StepArgs& a, const SC* scns, const
         if (!LDS) {
             sh.pflags[lane] = 0x7fffffffu;
         } else if (valid && a.brt) {
-            // second half of W2's golden-march re-check (its first wave-priority work)
+            // W3's part of W2's golden-march re-check (its first wave-priority work)
             const BrTab& T = a.brt[sh.scn[lane]];
             const BtHot* hot = LTAB ? hots + sh.scn[lane] : &T.hot;
             Body F = PF;
             advance_position(F);
             BtLane L = bt_start<LTAB>(T, hot, F.px, F.py);
-            const int k0 = S3 ? bt_third(T, 2) : bt_split(T);
+            const int k0 = EARLY ? BT_EARLY : S3 ? bt_third(T, 2) : bt_split(T);
             if (k0 < L.len) {
                 if (k0 >= 4) bt_window<LTAB>(hot, L, k0, F.px, F.py);
                 else bt_window_snap<LTAB>(T, hot, L, k0, F.px, F.py);

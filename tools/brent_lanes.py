@@ -10,7 +10,7 @@ per search scipy's fminbound step sequence (_optimize.py:2251-2398) with its dec
 and per wave of 64 consecutive slots: lanes in continuation, max / sum of continuation steps, so
 lane utilisation and packing alternatives can be priced before writing kernel code.
 
-    python tools/brent_lanes.py [--scenario corridor] [--envs 4096] [--warmup 300]
+    python tools/brent_lanes.py [--scenario corridor] [--envs 4096] [--warmup 300] [--early 7 10 13 16]
 """
 from __future__ import annotations
 
@@ -116,6 +116,120 @@ def table_dev(log, kind_len):
     return kind, min(len(log), n)
 
 
+def forced_len(L, kind):
+    """Length of the golden-march table of `kind` for a path of length L: the forced march (kind 0:
+    step 0 worse, then every step better; kind 1: every step better), capped at the table's 48 steps."""
+    a, bb = -10.0, L + 10.0
+    fulc = a + GOLD * (bb - a)
+    xf = nfc = fulc
+    e = 0.0
+    k = 0
+    xm = 0.5 * (a + bb)
+    tol1 = SQRT_EPS * abs(xf) + 1e-6 / 3.0
+    while abs(xf - xm) > (2 * tol1 - 0.5 * (bb - a)) and k < 48:
+        e = (a - xf) if xf >= xm else (bb - xf)
+        rat = GOLD * e
+        x = xf + (np.sign(rat) + (rat == 0)) * max(abs(rat), tol1)
+        le = not (kind == 0 and k == 0)
+        if le:
+            if x >= xf:
+                a = xf
+            else:
+                bb = xf
+            xf = x
+        else:
+            if x < xf:
+                a = x
+            else:
+                bb = x
+        k += 1
+        xm = 0.5 * (a + bb)
+        tol1 = SQRT_EPS * abs(xf) + 1e-6 / 3.0
+    return k
+
+
+def dist_to(sc, p):
+    """Distance from point p to the path of the C scenario `sc` as a function of u (the oracle's path)."""
+    import oracle
+
+    def f(u):
+        x, y = oracle.path_eval(sc, u)
+        dx, dy = x - p[0], y - p[1]
+        return math.sqrt(dx * dx + dy * dy)
+    return f
+
+
+def classify(sc, L, kind_len, px, py):
+    """(kind, dev, continuation steps) of the search from (px, py): dev == kind_len[kind] and no
+    continuation when the search follows its whole table."""
+    _, log = fminbound_log(dist_to(sc, (px, py)), -10.0, L + 10.0)
+    kind, dev = table_dev(log, kind_len)
+    return kind, dev, max(0, len(log) - dev)
+
+
+def up3(k):
+    return 3 * ((k + 2) // 3)
+
+
+def early_model(kind, dev, cont, kind_len, E, recheck_cost):
+    """The path wave's chain per wave of 64 lanes, as (re-check steps, continuation steps) on the
+    critical lane and their sum with a re-check step priced at `recheck_cost` continuation steps.
+    E = 0: today's split by halves (the path wave re-checks [1, split), waits for the other wave's
+    [split, len) -- 3 window distances, then passes of 3 -- and only then resumes any lane).
+    E > 0: the path wave re-checks [1, E) and resumes its early deviators at once; the lanes that
+    deviate in the other wave's [E, len) start when both waves are done."""
+    out = []
+    split = max(4, (kind_len[0] + 3) // 2) if E == 0 else E
+    for w in range(len(kind) // 64):
+        k, d, c = (x[64 * w:64 * w + 64] for x in (kind, dev, cont))
+        ln = np.array(kind_len)[k]
+        own = up3(int(np.minimum(d, np.minimum(split, ln)).max()) - 1)   # W2's passes run to the last lane
+        other = 3 + up3(int(np.maximum(ln - split, 0).max()))
+        if E == 0:
+            r, s = max(own, other), int(c.max())
+        else:
+            early = (d < np.minimum(split, ln)) & (c > 0)
+            late = ~early & (c > 0)
+            ce = int(c[early].max()) if early.any() else 0
+            cl = int(c[late].max()) if late.any() else 0
+            a = (own, ce)
+            b = (max(own, other), cl) if late.any() else (0, 0)
+            r, s = max(a, b, key=lambda x: x[0] * recheck_cost + x[1])
+        out.append((r, s, r * recheck_cost + s))
+    return np.array(out, float)
+
+
+def early_report(kind, dev, cont, kind_len, Es, recheck_cost):
+    """What `--early` prints: where the continuing lanes deviate and what an early start would buy."""
+    kind, dev, cont = (np.asarray(x) for x in (kind, dev, cont))
+    going = cont > 0
+    hist = np.bincount(dev[going], minlength=max(kind_len) + 1)
+    waves = cont.reshape(-1, 64)
+    longest = waves.argmax(1) + 64 * np.arange(len(waves))
+    longest = longest[waves.max(1) > 0]
+    res = {"table_len": list(kind_len), "split_today": max(4, (kind_len[0] + 3) // 2), "recheck_cost": recheck_cost,
+           "cont_lane_frac": float(going.mean()),
+           "dev_hist_continuing": {int(k): int(v) for k, v in enumerate(hist) if v},
+           "dev_of_wave_longest_lane": {int(k): int(v) for k, v in enumerate(np.bincount(dev[longest])) if v},
+           "wave_cont_max_mean": float(waves.max(1).mean()), "cont_max": int(cont.max()), "early": {}}
+    for E in Es:
+        cls = {"dev<E": going & (dev < E), "dev>=E": going & (dev >= E)}
+        m0, m = early_model(kind, dev, cont, kind_len, 0, recheck_cost), early_model(kind, dev, cont, kind_len, E,
+                                                                                       recheck_cost)
+        res["early"][int(E)] = {
+            "frac_continuing_below_E": float((dev[going] < E).mean()) if going.any() else 0.0,
+            "cont_by_class": {k: {"lanes": int(v.sum()), "mean": float(cont[v].mean()) if v.any() else 0.0,
+                                  "max": int(cont[v].max()) if v.any() else 0} for k, v in cls.items()},
+            "chain_today": {"recheck": float(m0[:, 0].mean()), "cont": float(m0[:, 1].mean()),
+                            "sum_mean": float(m0[:, 2].mean()), "sum_max": float(m0[:, 2].max())},
+            "chain_E": {"recheck": float(m[:, 0].mean()), "cont": float(m[:, 1].mean()),
+                        "sum_mean": float(m[:, 2].mean()), "sum_max": float(m[:, 2].max())},
+            "gain_mean": float(1.0 - m[:, 2].mean() / m0[:, 2].mean()),
+            "gain_slowest_wave": float(1.0 - m[:, 2].max() / m0[:, 2].max()),
+        }
+    return res
+
+
 def spec_iterations(steps, mode="worse"):
     """Wave-loop passes a lane needs for `steps` (log entries) when every pass evaluates the step's
     probe AND, speculatively, the next step's probe under the assumption that this step's new probe
@@ -148,6 +262,12 @@ def main():
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--warmup", type=int, default=300)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--early", type=int, nargs="+", metavar="E", default=None,
+                    help="early start of the continuation: the dev histogram of the continuing lanes, the dev of "
+                         "each wave's longest lane, continuation length by dev class and the modelled chain for "
+                         "today's split and for each E")
+    ap.add_argument("--recheck-cost", type=float, default=0.125,
+                    help="a table re-check step in continuation steps (~45 VALU against a 1.65-2.0 k cycle brent_step)")
     args = ap.parse_args()
 
     import oracle
@@ -168,47 +288,10 @@ def main():
     px, py = st[0], st[1]
     L = float(scn.path.length)
 
-    def fdist(p):
-        def f(u):
-            x, y = oracle.path_eval(sc, u)
-            dx, dy = x - p[0], y - p[1]
-            return math.sqrt(dx * dx + dy * dy)
-        return f
-
-    # table lengths: forced marches (kind 0: worse then better; kind 1: always better)
-    def forced_len(kind):
-        a, bb = -10.0, L + 10.0
-        fulc = a + GOLD * (bb - a)
-        xf = nfc = fulc
-        e = 0.0
-        k = 0
-        xm = 0.5 * (a + bb)
-        tol1 = SQRT_EPS * abs(xf) + 1e-6 / 3.0
-        while abs(xf - xm) > (2 * tol1 - 0.5 * (bb - a)) and k < 48:
-            e = (a - xf) if xf >= xm else (bb - xf)
-            rat = GOLD * e
-            x = xf + (np.sign(rat) + (rat == 0)) * max(abs(rat), tol1)
-            le = not (kind == 0 and k == 0)
-            if le:
-                if x >= xf:
-                    a = xf
-                else:
-                    bb = xf
-                xf = x
-            else:
-                if x < xf:
-                    a = x
-                else:
-                    bb = x
-            k += 1
-            xm = 0.5 * (a + bb)
-            tol1 = SQRT_EPS * abs(xf) + 1e-6 / 3.0
-        return k
-
-    kind_len = [forced_len(0), forced_len(1)]
+    kind_len = [forced_len(L, 0), forced_len(L, 1)]
     rows = []
     for i in range(args.envs):
-        _, log = fminbound_log(fdist((px[i], py[i])), -10.0, L + 10.0)
+        _, log = fminbound_log(dist_to(sc, (px[i], py[i])), -10.0, L + 10.0)
         kind, dev = table_dev(log, kind_len)
         cont = log[dev:] if dev < len(log) else []
         # trailing run of golden-worse steps in the continuation
@@ -254,6 +337,9 @@ def main():
         **{f"wave_{p}_max_spec_{m}": float(np.array([r[f"{p}_{m}"] for r in rows]).reshape(-1, 64).max(1).mean())
            for p in ("cont", "full") for m in ("worse", "better", "predict", "both")},
     }
+    if args.early:
+        res["early_start"] = early_report([r["kind"] for r in rows], [r["dev"] for r in rows], C, kind_len, args.early,
+                                          args.recheck_cost)
     print(json.dumps(res, indent=1))
     if args.out:
         json.dump(res, open(args.out, "w"), indent=1)
