@@ -967,6 +967,18 @@ constexpr int BT_EARLY = D2D_BT_EARLY;
 #define D2D_BT_EARLY_GRP 0
 #endif
 static_assert(BT_EARLY == 0 || (BT_EARLY >= 4 && BT_EARLY % 3 == 1 && BT_EARLY < BT_K), "BT_EARLY");
+// Riding (early start only, bt_finish_join): the lanes that followed [1, BT_EARLY) run plain brent_step
+// from the snapshot before step BT_EARLY beside the deviating lanes, in the continuation loop's idle
+// lanes, for at least BT_RIDE passes; a rider whose state then equals the table's snapshot bit for bit
+// has verified those steps itself, so the other wave re-checks [BT_EARLY + BT_RIDE, len) only.
+// 0: no riders (the early start as it was, instruction for instruction).
+// Measured at 65 536 corridor envs, us per step, interleaved: 0 25.97-26.08, 6 26.07-26.14, 9 25.93-26.04,
+// 12 25.71-25.84, 15 25.64-25.77 (kept), 18 25.74-25.84 (DESIGN.md "Where each lever stands").
+#ifndef D2D_BT_RIDE
+#define D2D_BT_RIDE 15
+#endif
+constexpr int BT_RIDE = D2D_BT_RIDE;
+static_assert(BT_RIDE >= 0 && (BT_RIDE == 0 || BT_EARLY > 0) && BT_EARLY + BT_RIDE < BT_K, "BT_RIDE");
 // three-way split: part p in {0, 1, 2} checks steps [bt_third(p), bt_third(p + 1)) (bt_third(0) = 1,
 // bt_third(3) = BT_K), as the fill kernel splits it
 __device__ __forceinline__ int bt_third(const BrTab& T, int p) {

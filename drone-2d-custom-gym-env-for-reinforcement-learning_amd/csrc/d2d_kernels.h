@@ -12,11 +12,12 @@
 //       store the state; velocity part of the observation (obs 0-2, 17-18) and of the reward
 //   W1  sensor part (obs 3..16, CA inputs); for envs that end: the spawn-state sensor part
 //   W2  path role: Brent closest point through the golden-march tables (steps [1, bt_split) of the
-//       table re-check; at full load [1, BT_EARLY), its deviating lanes resumed at once: the early
-//       start, bt_finish_join), obs 19..26, the position / path terms of the reward while the physics
-//       wave finishes (W0 takes the sum)
-//   W3  steps [bt_split, len) ([BT_EARLY, len)) of W2's table re-check; then, for envs that end, the
-//       spawn state and the spawn-state path part
+//       table re-check; at full load [1, BT_EARLY), its deviating lanes resumed at once and the lanes
+//       that followed riding their loop for BT_RIDE passes: the early start, bt_finish_join), obs
+//       19..26, the position / path terms of the reward while the physics wave finishes (W0 takes the
+//       sum)
+//   W3  steps [bt_split, len) ([BT_EARLY + BT_RIDE, len)) of W2's table re-check; then, for envs that
+//       end, the spawn state and the spawn-state path part
 //   (W1 and W3 take the spawn-state parts from the auto-reset observation cache when it is ready)
 //   epilogue (no barrier: an LDS count of the waves whose rows are written): W1-W3 store the 64x27
 //   f32 obs tile as one contiguous span; W0 writes reward / flags / info / bookkeeping.
@@ -349,13 +350,91 @@ __device__ __forceinline__ void tile_wait(const uint32_t& c, uint32_t n) {
 // scipy's evaluation count stays exact per lane: the first loop is capped at IT_JOIN passes (no lane
 // can reach 500 in it: an entry num is at most BT_K + 1), a lane carries its passes into brent_run
 // in num, and brent_run tests the count from the pass at which a lane could first reach 500.
+// Riders (BT_RIDE > 0): a lane that followed [1, BT_EARLY) does not sit out that loop but steps in it
+// from the snapshot before step BT_EARLY, and the loop runs for at least BT_RIDE passes while the wave
+// has one (a wave64 instruction costs the same with 11 lanes on or 64; the step is the plain
+// brent_step on the lane's own distances).  The other wave then re-checks [BT_EARLY + BT_RIDE, len)
+// only.  A rider moves along the table at the join only on proof: its state equals the table's
+// snapshot at the step it has reached (see there); otherwise it just keeps going from where it is.
+// The count: a rider enters with its snapshot's num (BT_EARLY + 1 <= BT_K + 1) and carries its passes
+// like any lane of the loop, a jump takes the target snapshot's num (<= BT_K + 1, with no passes
+// behind it), so every lane still enters brent_run with num <= BT_K + 1 + IT_JOIN, which is what
+// IT_FREE = 500 - (BT_K_MAX + 1) - IT_JOIN there assumes; BT_RIDE < IT_JOIN keeps the cap above the
+// riders' passes.
 template <bool LT, class SC>
 __device__ __forceinline__ double bt_finish_join(const SC& s, const BrTab& T, const BtHot* hot, const BtLane& L,
                                                  const uint32_t& fv, const uint32_t& dv, double px, double py,
                                                  int& iu) {
     constexpr int IT_JOIN = 200;
+    static_assert(BT_RIDE < IT_JOIN, "the riders' passes end below the first loop's cap");
     const PathK K = path_k(s);
     const bool early = L.dev < L.len;
+    if constexpr (BT_RIDE > 0) {
+        // a lane that followed [1, BT_EARLY) of a longer table rides: it starts from the snapshot before
+        // step BT_EARLY with the window it holds (the distances at fulc, nfc, xf: probes of the steps
+        // BT_EARLY - 3 .. BT_EARLY - 1, bt_window) and takes a step in every pass of the loop
+        const bool rider = !early & (L.len > BT_EARLY);
+        const bool any_rider = __ballot(rider) != 0ull;
+        Brent B;
+        bt_restore(T.snap[L.kind][rider ? BT_EARLY : L.dev], B);
+        if (__ballot(early) != 0ull) {
+            if (early) bt_restore_f<LT>(T.snap[L.kind][L.dev], hot, L.kind, px, py, B);
+        }
+        if (rider) {
+            B.ffulc = L.fa;
+            B.fnfc = L.fb;
+            B.fx = L.fc;
+        }
+        // the loop: as below while an early lane is open and the flag was not seen, and in any case for
+        // its first BT_RIDE passes when the wave has a rider (`go` is wave-uniform)
+        const bool in = early | rider;
+        uint32_t up = 0u;
+        int it = 0;
+        for (;; ++it) {
+            const bool open = in & brent_open(B);
+            const bool go = (any_rider & (it < BT_RIDE)) |
+                            ((__builtin_amdgcn_readfirstlane(up) == 0u) & (__ballot(early & open) != 0ull));
+            if (!(open & (it < IT_JOIN) & go)) break;
+            up = *(const volatile LdsU32*)&fv;
+            brent_step(s, K, px, py, B);
+        }
+        B.num += it;
+        flag_wait(fv);
+        // the join.  dv: the other wave's first differing step in [BT_EARLY + BT_RIDE, len) for a lane
+        // that follows the table up to there (len: none).  A rider that is still open has taken `it`
+        // >= BT_RIDE passes (only a closed lane or the cap, far above, leaves the loop sooner); if its
+        // whole search state equals the snapshot before step q = BT_EARLY + it bit for bit, it stands
+        // where the table stands, the other wave's verdict on [q, len) is about this lane, and it may
+        // jump to the snapshot before step dv >= q (the table's last one when dv == len) with the
+        // distances of that snapshot's probes -- the state it would reach step by step.  Every other
+        // rider keeps the state it has, which is exact whatever happened: one that left the table while
+        // riding, one whose dv < q, one that is closed.  (A table with len <= BT_EARLY + BT_RIDE: the
+        // other wave checks nothing, and a rider that follows it is closed by pass len - BT_EARLY.)
+        const uint32_t m = min((uint32_t)L.len, dv);
+        bool jump = false;
+        if (__ballot(rider & brent_open(B)) != 0ull) {
+            const int q = min(BT_EARLY + it, L.len);
+            const BtSnap& Q = T.snap[L.kind][q];
+            const auto same = [](double x, double y) { return __double_as_longlong(x) == __double_as_longlong(y); };
+            const bool eq = same(B.a, Q.a) & same(B.b, Q.b) & same(B.fulc, Q.fulc) & same(B.nfc, Q.nfc) &
+                            same(B.xf, Q.xf) & same(B.rat, Q.rat) & same(B.e, Q.e) & (B.ia == Q.ia) &
+                            (B.ib == Q.ib) & (B.ixf == Q.ixf);
+            jump = rider & brent_open(B) & (it >= BT_RIDE) & eq & (m >= (uint32_t)q);
+        }
+        // ... and, as below, the lanes of short tables (no riders) that deviate late or end open
+        const bool late = jump | (!in & ((dv < (uint32_t)L.len) | brent_active(B)));
+        if (__ballot(late) != 0ull) {
+            if (late) {
+                const BtSnap& S = T.snap[L.kind][m];
+                bt_restore(S, B);
+                if (brent_active(B)) bt_restore_f<LT>(S, hot, L.kind, px, py, B);
+            }
+        }
+        if (__ballot(brent_active(B)) != 0ull)
+            brent_run(s, K, px, py, B, nullptr, 500 - (BT_K_MAX + 1) - IT_JOIN);
+        iu = B.ixf;
+        return B.xf;
+    }
     // one restore for every lane: the snapshot before its first differing step, or the table's last
     // (L.dev == len: the lane followed the wave's part; what a lane that follows the whole table keeps)
     Brent B;
@@ -789,7 +868,8 @@ __device__ __forceinline__ void k1_body(const StepArgs& a, const SC* scns, const
             Body F = PF;
             advance_position(F);
             BtLane L = bt_start<LTAB>(T, hot, F.px, F.py);
-            const int k0 = EARLY ? BT_EARLY : S3 ? bt_third(T, 2) : bt_split(T);
+            // (early start: W2's riders verify [BT_EARLY, BT_EARLY + BT_RIDE) themselves, bt_finish_join)
+            const int k0 = EARLY ? BT_EARLY + BT_RIDE : S3 ? bt_third(T, 2) : bt_split(T);
             if (k0 < L.len) {
                 if (k0 >= 4) bt_window<LTAB>(hot, L, k0, F.px, F.py);
                 else bt_window_snap<LTAB>(T, hot, L, k0, F.px, F.py);

@@ -11,6 +11,7 @@ and per wave of 64 consecutive slots: lanes in continuation, max / sum of contin
 lane utilisation and packing alternatives can be priced before writing kernel code.
 
     python tools/brent_lanes.py [--scenario corridor] [--envs 4096] [--warmup 300] [--early 7 10 13 16]
+                                [--ride 6 9 12 15 18]
 """
 from __future__ import annotations
 
@@ -230,6 +231,58 @@ def early_report(kind, dev, cont, kind_len, Es, recheck_cost):
     return res
 
 
+def ride_report(kind, dev, cont, kind_len, E, Rs, recheck_cost, step_valu=150.0, check_valu=45.0):
+    """What `--ride` prints.  Under the early start (E) the lanes that followed [1, E) sit switched off
+    in the path wave's continuation loop; as riders they run brent_step from the snapshot before step E
+    in every pass, and the other wave re-checks [E + R, len) only.  Per wave of 64 lanes:
+
+      natural loop   the passes the loop runs today: the longest continuation among the lanes that
+                     deviate below E (0: the wave has none and only waits for the other wave)
+      added passes   max(0, R - natural loop) when the wave has a rider: passes run for the riders alone
+      saved steps    the other wave's re-check steps dropped, in its passes of three
+
+    and the wave's chain in continuation steps (a re-check step priced at `recheck_cost`): the first
+    loop, then the lanes that start at the join -- today every lane that deviates at or past E, after
+    the other wave's [E, len); with riders only those at or past E + R (a rider that deviates in
+    [E, E + R) has been stepping since pass 0 and needs dev - E + cont passes in all)."""
+    kind, dev, cont = (np.asarray(x) for x in (kind, dev, cont))
+    nw = len(kind) // 64
+    lens = np.array(kind_len)[kind]
+    early = (dev < np.minimum(E, lens)) & (cont > 0)
+    rider = ~(dev < np.minimum(E, lens)) & (lens > E)
+    W = lambda x: x[:64 * nw].reshape(nw, 64)
+    nat = np.where(W(early), W(cont), 0).max(1)
+    has_rider = W(rider).any(1)
+    own = up3(E - 1) * recheck_cost
+    res = {"E": E, "waves": nw, "rider_lane_frac": float(rider.mean()), "waves_with_rider": float(has_rider.mean()),
+           "natural_loop": {"mean": float(nat.mean()), "zero_frac": float((nat == 0).mean()),
+                            "quantiles": {str(q): float(np.quantile(nat, q / 100.0)) for q in (5, 10, 25, 50, 75, 90, 100)},
+                            "hist": {int(k): int(v) for k, v in enumerate(np.bincount(nat)) if v}},
+           "step_valu": step_valu, "check_valu": check_valu, "ride": {}}
+    for R in [0] + [r for r in Rs if r > 0]:
+        other = np.array([3 + up3(int(max(l.max() - E - R, 0))) if l.max() > E + R else 0 for l in W(lens)], float)
+        other0 = np.array([3 + up3(int(max(l.max() - E, 0))) if l.max() > E else 0 for l in W(lens)], float)
+        added = np.where(has_rider, np.maximum(0, R - nat), 0) if R else np.zeros(nw)
+        loop = nat + added
+        # the lanes that continue but not from below E start at the join: the loop has ended and the
+        # other wave, which runs beside the path wave's own part, has raised its flag
+        mid = W(~early & (cont > 0) & (dev < E + R)) if R else np.zeros((nw, 64), bool)
+        late = W(~early & (cont > 0)) & ~mid
+        mid_end = own + np.where(mid, W(dev) - E + W(cont), 0).max(1)
+        flag = other * recheck_cost
+        join = np.maximum(own + loop, flag)
+        late_end = np.where(late.any(1), join + np.where(late, W(cont), 0).max(1), 0)
+        chain = np.maximum(np.maximum(join, mid_end), late_end)  # (the wave always waits for the flag)
+        res["ride"][int(R)] = {
+            "waves_loop_shorter_than_R": float((has_rider & (nat < R)).mean()),
+            "added_passes_mean": float(added.mean()), "added_passes_total": int(added.sum()),
+            "saved_steps_mean": float((other0 - other).mean()),
+            "valu_per_wave_pair": float((added * step_valu - (other0 - other) * check_valu).mean()),
+            "chain_mean": float(chain.mean()), "chain_p90": float(np.quantile(chain, 0.9)), "chain_max": float(chain.max()),
+        }
+    return res
+
+
 def spec_iterations(steps, mode="worse"):
     """Wave-loop passes a lane needs for `steps` (log entries) when every pass evaluates the step's
     probe AND, speculatively, the next step's probe under the assumption that this step's new probe
@@ -266,6 +319,11 @@ def main():
                     help="early start of the continuation: the dev histogram of the continuing lanes, the dev of "
                          "each wave's longest lane, continuation length by dev class and the modelled chain for "
                          "today's split and for each E")
+    ap.add_argument("--ride", type=int, nargs="+", metavar="R", default=None,
+                    help="table followers riding the continuation loop (early start at --ride-early): each "
+                         "wave's natural loop length, and for each R the passes riders add where it is shorter "
+                         "than R, the re-check steps the other wave drops and the modelled chain")
+    ap.add_argument("--ride-early", type=int, default=16, help="E of --ride (BT_EARLY)")
     ap.add_argument("--recheck-cost", type=float, default=0.125,
                     help="a table re-check step in continuation steps (~45 VALU against a 1.65-2.0 k cycle brent_step)")
     args = ap.parse_args()
@@ -340,6 +398,9 @@ def main():
     if args.early:
         res["early_start"] = early_report([r["kind"] for r in rows], [r["dev"] for r in rows], C, kind_len, args.early,
                                           args.recheck_cost)
+    if args.ride:
+        res["ride"] = ride_report([r["kind"] for r in rows], [r["dev"] for r in rows], C, kind_len, args.ride_early,
+                                  args.ride, args.recheck_cost)
     print(json.dumps(res, indent=1))
     if args.out:
         json.dump(res, open(args.out, "w"), indent=1)
