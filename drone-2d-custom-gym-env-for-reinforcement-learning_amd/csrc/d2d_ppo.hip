@@ -174,7 +174,8 @@ constexpr int TPS = 4, MLP_SPB = MLP_BLOCK / TPS, UNITS = HID / TPS;
 constexpr int FM_SPB = 32, FM_TILES = 2, XS = OBS + 2, HS = HID + 1;  // LDS row strides: bank spread
 // tanh for the matrix-core forward: |x| < 0.25 an odd Taylor polynomial (next term
 // < 3e-8 relative), else (1 - t) / (1 + t) with t = exp(-2 |x|) from v_exp_f32 and v_rcp_f32 (no
-// cancellation: 1 - t >= 0.39): a few ulp, 15 instructions instead of the library's ~60, which made
+// cancellation: 1 - t >= 0.39): a few ulp (3.1 at most over 262 144 points, DESIGN.md "PPO update:
+// what the tests pin"), 15 instructions instead of the library's ~60, which made
 // the hidden layers' activations the longest part of a forward workgroup.
 __device__ __forceinline__ float ftanh(float x) {
     const float ax = fabsf(x), x2 = x * x;
@@ -484,6 +485,22 @@ __global__ void counter_add_kernel(uint64_t* c, uint64_t k) {
     if (threadIdx.x == 0) c[0] += k;
 }
 
+// The Gaussian log-density part of the loss head in double: z = (a - mean) / sigma and logp - old_logp,
+// each rounded to float once.  In float32 the subtraction's and the log-density's roundings, scaled by
+// 1 / sigma and by z, were the largest part of the head's error at a small sigma.  (The ratio stays
+// expf of the float log-ratio: a double exp per sample made the fused update 2 % longer.)
+struct HeadZ {
+    float z0, z1, log_ratio, ratio;
+};
+__device__ __forceinline__ HeadZ head_z(float a0, float a1, double mu0, double mu1, float ls0, float ls1,
+                                        double is0, double is1, float old_logp) {
+    constexpr double HALF_LOG_2PI_D = 0.91893853320467274178;
+    const double z0 = ((double)a0 - mu0) * is0, z1 = ((double)a1 - mu1) * is1;
+    const double logp = (-0.5 * z0 * z0 - (double)ls0 - HALF_LOG_2PI_D) + (-0.5 * z1 * z1 - (double)ls1 - HALF_LOG_2PI_D);
+    const double lr = logp - (double)old_logp;
+    return HeadZ{(float)z0, (float)z1, (float)lr, expf((float)lr)};
+}
+
 // the loss head (policy: the clipped surrogate's d/d mean; value: the squared error's d/d V) and the
 // backward pass to the two hidden layers' output gradients; per-workgroup partial sums
 // (sum min(s1, s2), sum (R - V)^2, #clipped, sum dL/dlogp (z0^2 - 1), sum dL/dlogp (z1^2 - 1)):
@@ -518,7 +535,9 @@ __global__ __launch_bounds__(MLP_BLOCK) void mlp_backward_kernel(MlpPair P, int 
     double q[5] = {0.0, 0.0, 0.0, 0.0, 0.0};
     float go0 = 0.0f, go1 = 0.0f;
     if (blockIdx.y == 0) {
-        float adv_mean = 0.0f, adv_inv = 1.0f;
+        // (the minibatch mean and 1 / std stay double: rounded to float, the mean shifts every
+        // normalised advantage the same way, which the policy loss, a sum near zero, shows)
+        double adv_mean = 0.0, adv_inv = 1.0;
         if (normalize) {
             double s = 0.0, sq = 0.0;
             for (int b = threadIdx.x; b < nbs; b += blockDim.x) {
@@ -530,17 +549,41 @@ __global__ __launch_bounds__(MLP_BLOCK) void mlp_backward_kernel(MlpPair P, int 
             s = sv[0];
             sq = sv[1];
             const double mu = s / m, var = (sq - s * mu) / (m > 1 ? m - 1 : 1);
-            adv_mean = (float)mu;
-            adv_inv = 1.0f / ((float)sqrt(var > 0.0 ? var : 0.0) + 1e-8f);
+            adv_mean = mu;
+            adv_inv = 1.0 / (sqrt(var > 0.0 ? var : 0.0) + 1e-8);
         }
-        if (live) {  // both halves compute the head; the first one records it
+        if (live) {  // the sample's TPS threads all compute the head; the first one records it
             const int64_t j = idx[i];
             const float ls0 = log_std[0], ls1 = log_std[1];
             const float is0 = expf(-ls0), is1 = expf(-ls1);
-            const float z0 = (act[2 * j] - N.out[2 * i]) * is0, z1 = (act[2 * j + 1] - N.out[2 * i + 1]) * is1;
-            const float logp = (-0.5f * z0 * z0 - ls0 - HALF_LOG_2PI) + (-0.5f * z1 * z1 - ls1 - HALF_LOG_2PI);
-            const float a = normalize ? (adv[j] - adv_mean) * adv_inv : adv[j];
-            const float ratio = expf(logp - old_logp[j]);
+            // the action mean from h2 in double, not the forward's stored float (whose rounding times
+            // 1 / sigma times z is of the size of the head's whole error): each of the sample's TPS
+            // threads sums its 16 units, as the fused kernel does
+            double mu0 = 0.0, mu1 = 0.0;
+            {
+                const float* h2 = N.h2 + (size_t)i * HID;
+#pragma unroll
+                for (int jj = 0; jj < UNITS; jj += 4) {
+                    const float4 hv = *reinterpret_cast<const float4*>(h2 + ub(jj));
+                    const float hh[4] = {hv.x, hv.y, hv.z, hv.w};
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        mu0 += (double)N.w3[ub(jj) + u] * (double)hh[u];
+                        mu1 += (double)N.w3[HID + ub(jj) + u] * (double)hh[u];
+                    }
+                }
+                mu0 += __shfl_xor(mu0, 1, 64);
+                mu1 += __shfl_xor(mu1, 1, 64);
+                mu0 += __shfl_xor(mu0, 2, 64);
+                mu1 += __shfl_xor(mu1, 2, 64);
+                mu0 += (double)N.b3[0];
+                mu1 += (double)N.b3[1];
+            }
+            const HeadZ hz = head_z(act[2 * j], act[2 * j + 1], mu0, mu1, ls0, ls1, exp(-(double)ls0),
+                                    exp(-(double)ls1), old_logp[j]);
+            const float z0 = hz.z0, z1 = hz.z1;
+            const float a = normalize ? (float)(((double)adv[j] - adv_mean) * adv_inv) : adv[j];
+            const float ratio = hz.ratio;
             const float s1 = a * ratio, s2 = a * fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
             const float g_lp = (s1 <= s2) ? a * ratio * (-1.0f / m) : 0.0f;
             go0 = g_lp * z0 * is0;
@@ -729,7 +772,7 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_grad_kernel(FusedKArgs<CTL> 
         const int r = e / (HID + 1), j = e % (HID + 1);
         w3s[r][j] = r < od ? (j < HID ? N.w3[r * HID + j] : N.b3[r]) : 0.0f;
     }
-    float adv_mean = 0.0f, adv_inv = 1.0f;
+    double adv_mean = 0.0, adv_inv = 1.0;  // (double: see mlp_backward_kernel)
     if (net == 0 && A.normalize) {
         double sm = 0.0, sq = 0.0;
         for (int b = tid; b < A.nbs; b += 256) {
@@ -739,10 +782,11 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_grad_kernel(FusedKArgs<CTL> 
         double sv[2] = {sm, sq};
         block_sum_n(sv, red);
         const double mu = sv[0] / m, var = (sv[1] - sv[0] * mu) / (m > 1 ? m - 1 : 1);
-        adv_mean = (float)mu;
-        adv_inv = 1.0f / ((float)sqrt(var > 0.0 ? var : 0.0) + 1e-8f);
+        adv_mean = mu;
+        adv_inv = 1.0 / (sqrt(var > 0.0 ? var : 0.0) + 1e-8);
     }
     const float ls0 = A.log_std[0], ls1 = A.log_std[1], is0 = expf(-ls0), is1 = expf(-ls1);
+    const double is0d = (double)is0, is1d = (double)is1;  // (the float 1 / sigma, as the torch restatement has it)
     f32x16 dw2 = {}, dw1 = {};
     float db1 = 0.0f, db2 = 0.0f, dw3a = 0.0f, dw3b = 0.0f, db3a = 0.0f, db3b = 0.0f;
     double q[NQ];
@@ -796,31 +840,33 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_grad_kernel(FusedKArgs<CTL> 
         if (first) PPO_STAMP(3);
         {  // the outputs (four threads per sample, 16 units each) and the loss head (the first of the four)
             const int i = tid >> 2, pq = tid & 3, s = s0 + i;
-            float o0 = 0.0f, o1 = 0.0f;
+            // in double: at a small sigma the loss head multiplies the mean's error by 1 / sigma (z) and
+            // again by z (log-density), and a float32 sum's rounding then shows in the gradient
+            double o0 = 0.0, o1 = 0.0;
 #pragma unroll
             for (int jj = 0; jj < HID / 4; ++jj) {
                 const int j = pq * (HID / 4) + jj;
-                const float hv = h2s[i][j];
-                o0 += w3s[0][j] * hv;
-                o1 += w3s[1][j] * hv;
+                const double hv = (double)h2s[i][j];
+                o0 += (double)w3s[0][j] * hv;
+                o1 += (double)w3s[1][j] * hv;
             }
             o0 += __shfl_xor(o0, 1, 64);
             o1 += __shfl_xor(o1, 1, 64);
             o0 += __shfl_xor(o0, 2, 64);
             o1 += __shfl_xor(o1, 2, 64);
-            o0 += w3s[0][HID];
-            o1 += w3s[1][HID];
+            o0 += (double)w3s[0][HID];
+            o1 += (double)w3s[1][HID];
             if (pq == 0) {
                 float g0 = 0.0f, g1v = 0.0f;
                 if (s < m) {
                     const int64_t j = rows[i];
                     if (net == 0) {
-                        const float z0 = (A.act[2 * j] - o0) * is0, z1 = (A.act[2 * j + 1] - o1) * is1;
-                        const float logp =
-                            (-0.5f * z0 * z0 - ls0 - HALF_LOG_2PI) + (-0.5f * z1 * z1 - ls1 - HALF_LOG_2PI);
-                        const float a = A.normalize ? (A.adv[j] - adv_mean) * adv_inv : A.adv[j];
-                        const float log_ratio = logp - A.old_logp[j];
-                        const float ratio = expf(log_ratio);
+                        const HeadZ hz = head_z(A.act[2 * j], A.act[2 * j + 1], o0, o1, ls0, ls1, is0d, is1d,
+                                                A.old_logp[j]);
+                        const float z0 = hz.z0, z1 = hz.z1;
+                        const float a = A.normalize ? (float)(((double)A.adv[j] - adv_mean) * adv_inv) : A.adv[j];
+                        const float log_ratio = hz.log_ratio;
+                        const float ratio = hz.ratio;
                         const float s1 = a * ratio, s2 = a * fminf(fmaxf(ratio, 1.0f - clip), 1.0f + clip);
                         const float g_lp = (s1 <= s2) ? a * ratio * (-1.0f / m) : 0.0f;
                         g0 = g_lp * z0 * is0;
@@ -831,11 +877,11 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_grad_kernel(FusedKArgs<CTL> 
                         q[4] += (double)g_lp * (z1 * z1 - 1.0f);
                         if constexpr (CTL) q[5] += (double)((ratio - 1.0f) - log_ratio);
                     } else {
-                        float err = A.ret[j] - o0;
+                        float err = (float)((double)A.ret[j] - o0);
                         bool pass = true;
                         if constexpr (CTL) {
                             if (clip_vf >= 0.0f) {  // SB3 clip_range_vf: the prediction clipped around the old value
-                                const float old = K.old_val[j], d = o0 - old;
+                                const float old = K.old_val[j], d = (float)(o0 - (double)old);
                                 err = A.ret[j] - (old + fminf(fmaxf(d, -clip_vf), clip_vf));
                                 pass = fabsf(d) <= clip_vf;  // torch.clamp's gradient: bounds included
                             }
@@ -946,8 +992,8 @@ constexpr int ADAM_THREADS = 1024, ADAM_PER_THREAD = 16;  // n <= 16 384 paramet
 template <bool CTL>
 __device__ __forceinline__ void adam_body(int n, float* __restrict__ p, float* __restrict__ g,
                                           float* __restrict__ m1, float* __restrict__ m2, float* __restrict__ t,
-                                          float lr, float b1, float b2, float eps, float max_norm,
-                                          d2d_ppo_ctl* ctl = nullptr) {
+                                          float lr, float b1, float b2, float omb1, float omb2, float eps,
+                                          float max_norm, d2d_ppo_ctl* ctl = nullptr) {
     __shared__ double red[ADAM_THREADS / 64];
     // the moments and parameters are loaded with the gradient, ahead of the norm's reduction, so
     // the update below waits on no memory
@@ -987,8 +1033,8 @@ __device__ __forceinline__ void adam_body(int n, float* __restrict__ p, float* _
             const float gi = gv[k] * coef;
             g[i] = gi;
             const float a0 = a0v[k], v0 = v0v[k];
-            const float a = a0 + (1.0f - b1) * (gi - a0);  // exp_avg.lerp_(grad, 1 - beta1)
-            const float v = v0 * b2 + (1.0f - b2) * gi * gi;
+            const float a = a0 + omb1 * (gi - a0);  // exp_avg.lerp_(grad, 1 - beta1)
+            const float v = v0 * b2 + omb2 * gi * gi;
             m1[i] = a;
             m2[i] = v;
             p[i] = p0v[k] - a * lr_t / (sqrtf(v) / bc2s + eps);
@@ -1000,14 +1046,15 @@ __device__ __forceinline__ void adam_body(int n, float* __restrict__ p, float* _
 __global__ __launch_bounds__(ADAM_THREADS) void adam_kernel(int n, float* __restrict__ p, float* __restrict__ g,
                                                             float* __restrict__ m1, float* __restrict__ m2,
                                                             float* __restrict__ t, float lr, float b1, float b2,
-                                                            float eps, float max_norm) {
-    adam_body<false>(n, p, g, m1, m2, t, lr, b1, b2, eps, max_norm);
+                                                            float omb1, float omb2, float eps, float max_norm) {
+    adam_body<false>(n, p, g, m1, m2, t, lr, b1, b2, omb1, omb2, eps, max_norm);
 }
 __global__ __launch_bounds__(ADAM_THREADS) void adam_ctl_kernel(int n, float* __restrict__ p, float* __restrict__ g,
                                                                 float* __restrict__ m1, float* __restrict__ m2,
-                                                                float* __restrict__ t, float b1, float b2, float eps,
-                                                                float max_norm, d2d_ppo_ctl* ctl) {
-    adam_body<true>(n, p, g, m1, m2, t, 0.0f, b1, b2, eps, max_norm, ctl);
+                                                                float* __restrict__ t, float b1, float b2, float omb1,
+                                                                float omb2, float eps, float max_norm,
+                                                                d2d_ppo_ctl* ctl) {
+    adam_body<true>(n, p, g, m1, m2, t, 0.0f, b1, b2, omb1, omb2, eps, max_norm, ctl);
 }
 
 // (A spread Adam -- ceil(n / 1024) workgroups, each computing the norm -- measured 8.1 us + 3.9 us for
@@ -1144,6 +1191,15 @@ __global__ __launch_bounds__(256) void grad_reduce_ctl_kernel(int n_chunks, int 
 
 inline int32_t rc(hipError_t e) { return e == hipSuccess ? 0 : (int32_t)e; }
 
+// The moment updates' weight 1 - beta as torch.optim.Adam has it: the float nearest to 1 - beta of the
+// decimal beta the caller means (0.9, 0.999), not 1 - (float)beta, which for 0.999 is 1.3e-5 (relative)
+// smaller and left exp_avg_sq that far from torch's.  beta arrives as a float (the ABI); when it is the
+// float nearest to a number of at most six decimals, that number is taken.
+inline float one_minus_beta(float beta) {
+    const double b = (double)beta, r = std::nearbyint(b * 1e6) / 1e6;
+    return (float)(1.0 - ((float)r == beta ? r : b));
+}
+
 }  // namespace
 
 extern "C" {
@@ -1176,7 +1232,7 @@ int32_t d2d_ppo_adam(int32_t n, float* p, float* g, float* m1, float* m2, float*
     if (n <= 0) return 0;
     if (n > ADAM_THREADS * ADAM_PER_THREAD) return (int32_t)hipErrorInvalidValue;
     hipLaunchKernelGGL(adam_kernel, dim3(1), dim3(ADAM_THREADS), 0, (hipStream_t)stream, n, p, g, m1, m2, t, lr, b1,
-                       b2, eps, max_norm);
+                       b2, one_minus_beta(b1), one_minus_beta(b2), eps, max_norm);
     return rc(hipGetLastError());
 }
 
@@ -1361,7 +1417,7 @@ int32_t d2d_ppo_adam_ctl(int32_t n, float* p, float* g, float* m1, float* m2, fl
     if (n <= 0) return 0;
     if (n > ADAM_THREADS * ADAM_PER_THREAD || !ctl) return (int32_t)hipErrorInvalidValue;
     hipLaunchKernelGGL(adam_ctl_kernel, dim3(1), dim3(ADAM_THREADS), 0, (hipStream_t)stream, n, p, g, m1, m2, t, b1,
-                       b2, eps, max_norm, ctl);
+                       b2, one_minus_beta(b1), one_minus_beta(b2), eps, max_norm, ctl);
     return rc(hipGetLastError());
 }
 

@@ -40,7 +40,9 @@ int32_t d2d_ppo_head_finish(int32_t m, int32_t n_blocks, const float* partial, c
 /* clip_grad_norm_(max_norm) then one torch.optim.Adam step (betas b1, b2, eps; bias corrections
  * from the step counter *t, which is incremented) over n parameters p with gradients g and
  * moments m1, m2; g is clipped in place, as torch clips .grad.  One workgroup, n <= 16 384 (the
- * policy has ~10 k parameters). */
+ * policy has ~10 k parameters).  The moments are scaled as torch scales them, by the float nearest to
+ * 1 - beta of the decimal beta that b1 / b2 round (0.9, 0.999), not by 1 - (float)beta; the bias
+ * corrections are float32 (powf of the float beta). */
 int32_t d2d_ppo_adam(int32_t n, float* p, float* g, float* m1, float* m2, float* t, float lr, float b1, float b2,
                      float eps, float max_norm, void* stream);
 
@@ -75,7 +77,10 @@ int32_t d2d_ppo_wgrad_chunks(int32_t m);
  * finished by d2d_ppo_head_finish with n_blocks = d2d_ppo_mlp_partial_rows(m)) and the hidden layers' output gradients g2, g1.
  * The head: Gaussian log-density of act under (mean, exp(log_std)), ratio = exp(logp - old_logp),
  * clipped surrogate with advantages normalised by d2d_ppo_adv_stats' partials (normalize != 0),
- * squared value error scaled by vf_coef. */
+ * squared value error scaled by vf_coef.  The head takes the action mean as a double sum over h2
+ * (mlp_backward sums it again instead of reading `out`), z = (a - mean) / sigma, logp - old_logp and
+ * the normalised advantage in double and rounds each to float once (at a small sigma their float32
+ * roundings, times 1 / sigma and z, were the gradient's largest error). */
 int32_t d2d_ppo_mlp_forward(int32_t m, const int64_t* idx, const float* obs, const float* const* weights,
                             float* const* bufs, float* xg, void* stream);
 /* mlp_forward plus d2d_ppo_adv_stats' partials into ws from the same launch (adv != NULL; the
