@@ -55,6 +55,29 @@ class NativeError(RuntimeError):
     pass
 
 
+def check_version(lib: C.CDLL, path: str, version_fn: str, expected: int, error, message: str | None = None):
+    """Raise ``error`` unless ``lib``'s ``version_fn()`` returns ``expected``."""
+    v = getattr(lib, version_fn)()
+    if v != expected:
+        raise error(message or f"{path}: ABI version {v}, expected {expected}")
+
+
+def bind(path: str, signatures: dict, version_fn: str, expected: int, error, message: str | None = None) -> C.CDLL:
+    """Open one of the package's HIP libraries: ``signatures`` ({name: (restype, argtypes)}) applied,
+    ``version_fn`` checked against ``expected`` (``error``, the caller's class, raised otherwise)."""
+    # torch must own the HIP runtime first: its bundled libamdhip64 has the same soname, so the
+    # library below then binds to that one runtime (one HIP context for torch and the envs).
+    import torch  # noqa: F401
+
+    lib = C.CDLL(path)
+    for name, (res, args) in signatures.items():
+        fn = getattr(lib, name)
+        fn.restype = res
+        fn.argtypes = args
+    check_version(lib, path, version_fn, expected, error, message)
+    return lib
+
+
 def load(path: str | None = None) -> C.CDLL:
     """Load (once) the HIP library. Raises ``NativeError`` if it is absent or ABI-mismatched."""
     global _lib
@@ -66,18 +89,7 @@ def load(path: str | None = None) -> C.CDLL:
     if not os.path.exists(p):
         raise NativeError(f"{p} not found: the HIP extension is not built "
                           f"(run `python -c 'import __graft_entry__ as g; g.build()'`)")
-    # torch must own the HIP runtime first: its bundled libamdhip64 has the same soname, so the
-    # library below then binds to that one runtime (one HIP context for torch and the envs).
-    import torch  # noqa: F401
-
-    lib = C.CDLL(p)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.d2d_abi_version()
-    if v != abi.ABI_VERSION:
-        raise NativeError(f"{p}: ABI version {v}, expected {abi.ABI_VERSION}")
+    lib = bind(p, SIGNATURES, "d2d_abi_version", abi.ABI_VERSION, NativeError)
     if path is None:
         _lib = lib
     else:

@@ -39,20 +39,19 @@ class EvalError(RuntimeError):
     pass
 
 
+SIGNATURES = {
+    "d2d_eval_abi_version": (C.c_int32, []),
+    "d2d_eval_step": (C.c_int32, [C.POINTER(D2DEvalStepArgs), _VP]),
+}
+
 _lib = None
 
 
 def bind(path: str) -> C.CDLL:
     """The library at ``path`` with its signatures set and its ABI version checked."""
-    from . import _native  # noqa: F401  (torch owns the HIP runtime first, as in ppo.ppo_native)
+    from . import _native
 
-    lib = C.CDLL(path)
-    lib.d2d_eval_abi_version.restype, lib.d2d_eval_abi_version.argtypes = C.c_int32, []
-    lib.d2d_eval_step.restype, lib.d2d_eval_step.argtypes = C.c_int32, [C.POINTER(D2DEvalStepArgs), _VP]
-    v = lib.d2d_eval_abi_version()
-    if v != ABI_VERSION:
-        raise EvalError(f"{path}: ABI version {v}, expected {ABI_VERSION}")
-    return lib
+    return _native.bind(path, SIGNATURES, "d2d_eval_abi_version", ABI_VERSION, EvalError)
 
 
 def load() -> C.CDLL:

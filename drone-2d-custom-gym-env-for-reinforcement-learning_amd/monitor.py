@@ -44,23 +44,22 @@ class MonitorError(RuntimeError):
     pass
 
 
+_I32 = C.c_int32
+SIGNATURES = {
+    "d2d_monitor_abi_version": (_I32, []),
+    "d2d_monitor_step": (_I32, [C.POINTER(D2DMonitorStepArgs), _VP]),
+    "d2d_monitor_flush": (_I32, [_VP, _I32, _VP, _VP]),
+    "d2d_monitor_reset": (_I32, [_I32, _VP, _VP, _VP, _I32, _VP]),
+}
+
 _lib = None
 
 
 def bind(path: str) -> C.CDLL:
     """The library at ``path`` with its signatures set and its ABI version checked."""
-    from . import _native  # noqa: F401  (torch owns the HIP runtime first, as in ppo.ppo_native)
+    from . import _native
 
-    lib = C.CDLL(path)
-    i32 = C.c_int32
-    lib.d2d_monitor_abi_version.restype, lib.d2d_monitor_abi_version.argtypes = i32, []
-    lib.d2d_monitor_step.restype, lib.d2d_monitor_step.argtypes = i32, [C.POINTER(D2DMonitorStepArgs), _VP]
-    lib.d2d_monitor_flush.restype, lib.d2d_monitor_flush.argtypes = i32, [_VP, i32, _VP, _VP]
-    lib.d2d_monitor_reset.restype, lib.d2d_monitor_reset.argtypes = i32, [i32, _VP, _VP, _VP, i32, _VP]
-    v = lib.d2d_monitor_abi_version()
-    if v != ABI_VERSION:
-        raise MonitorError(f"{path}: ABI version {v}, expected {ABI_VERSION}")
-    return lib
+    return _native.bind(path, SIGNATURES, "d2d_monitor_abi_version", ABI_VERSION, MonitorError)
 
 
 def load() -> C.CDLL:

@@ -62,18 +62,10 @@ def load() -> C.CDLL:
         from ._build import build_render
 
         build_render()
-    import torch  # noqa: F401  (torch owns the HIP runtime first, as in _native.load)
+    from . import _native
 
-    lib = C.CDLL(LIB_PATH)
-    for name, (res, args) in SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.restype = res
-        fn.argtypes = args
-    v = lib.d2dr_abi_version()
-    if v != ABI_VERSION:
-        raise RenderError(f"{LIB_PATH}: ABI version {v}, expected {ABI_VERSION}")
-    _lib = lib
-    return lib
+    _lib = _native.bind(LIB_PATH, SIGNATURES, "d2dr_abi_version", ABI_VERSION, RenderError)
+    return _lib
 
 
 def check(code: int, what: str) -> None:

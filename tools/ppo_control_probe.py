@@ -2,13 +2,14 @@
 """The measurements of DESIGN.md "PPO control" (one MI355X; a record, the only bar is on `train`'s
 default path).
 
-    python tools/ppo_control_probe.py train [--parent-tree DIR] [--runs 5] [--updates 30]
+    python tools/ppo_control_probe.py train [--parent-tree DIR [--parent-control]] [--runs 5] [--updates 30]
     python tools/ppo_control_probe.py stop  [--rounds 7]
 
 ``train``: DESIGN.md "Monitor"'s protocol -- ``tools/train_ppo.py``, 65 536 corridor envs, 30 updates, a
 fresh process per run, the median env-steps/s over the updates after the graph captures (update >= 3)
 -- for this tree's default path, this tree with ``--target-kl inf`` (the control path, never stopping)
-and, with ``--parent-tree``, the parent commit's built tree, alternating in one call.
+and, with ``--parent-tree``, the parent commit's built tree (``--parent-control``: that tree with
+``--target-kl inf`` as well), alternating in one call.
 ``stop``: one captured update of the headline configuration (320 minibatch steps) that runs in full
 against one that stops at its first minibatch (``target_kl = -1``), the same graph replayed.
 Results: ``profiles/ppo_control/<mode>_probe.json`` (``--out``).
@@ -24,6 +25,7 @@ import sys
 import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+ARMS = ("parent", "parent_control", "default", "control")
 
 
 def _train_run(tree: str, a, extra=()) -> dict:
@@ -43,17 +45,20 @@ def _train_run(tree: str, a, extra=()) -> dict:
 
 
 def train_probe(a) -> dict:
-    out = {"envs": a.envs, "updates": a.updates, "runs": a.runs, "default": [], "control": [], "parent": []}
+    out = {"envs": a.envs, "updates": a.updates, "runs": a.runs, "default": [], "control": [], "parent": [],
+           "parent_control": []}
     _train_run(REPO, a)  # a first run nobody counts: the box's caches
     for k in range(a.runs):
         if a.parent_tree:
             out["parent"].append(_train_run(os.path.abspath(a.parent_tree), a))
+        if a.parent_tree and a.parent_control:
+            out["parent_control"].append(_train_run(os.path.abspath(a.parent_tree), a, ("--target-kl", "inf")))
         out["default"].append(_train_run(REPO, a))
         out["control"].append(_train_run(REPO, a, ("--target-kl", "inf")))
-        print(json.dumps({"run": k, **{n: out[n][-1] for n in ("parent", "default", "control") if out[n]}}), flush=True)
+        print(json.dumps({"run": k, **{n: out[n][-1] for n in ARMS if out[n]}}), flush=True)
     for key in ("whole_run", "steady_median", "train_s_median"):
         out[key] = {}
-        for n in ("parent", "default", "control"):
+        for n in ARMS:
             v = [x[key] for x in out[n]]
             if v:
                 out[key].update({n + "_median": statistics.median(v), n + "_min": min(v), n + "_max": max(v)})
@@ -61,6 +66,9 @@ def train_probe(a) -> dict:
         if a.parent_tree:
             out[key]["default_inside_parent_spread"] = (out[key]["parent_min"] <= out[key]["default_median"]
                                                         <= out[key]["parent_max"])
+        if out["parent_control"]:
+            out[key]["control_inside_parent_spread"] = (out[key]["parent_control_min"] <= out[key]["control_median"]
+                                                        <= out[key]["parent_control_max"])
     return out
 
 
@@ -107,6 +115,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=7)
     ap.add_argument("--updates", type=int, default=30)
     ap.add_argument("--parent-tree", default=None)
+    ap.add_argument("--parent-control", action="store_true", help="also run the parent tree with --target-kl inf")
     ap.add_argument("--out", default=None, help="result file (default: profiles/ppo_control/<mode>_probe.json)")
     a = ap.parse_args()
     res = train_probe(a) if a.mode == "train" else stop_probe(a)
