@@ -21,6 +21,9 @@ from . import abi
 ABI_VERSION = 1
 NOISE_NONE, NOISE_GIVEN, NOISE_PHILOX = 0, 1, 2
 NOISE_TAG = 0x45560000
+BANK_VERSION = 1
+BANK_STRIDE = 6084  # floats per policy in a bank: W1, b1, W2, b2, W3, b3, log_std (include/d2d_eval.h)
+_BANK_SHAPES = ((64, 27), (64,), (64, 64), (64,), (2, 64), (2,), (2,))
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib", "libd2d_eval.so")
 
 _VP = C.c_void_p
@@ -35,6 +38,11 @@ class D2DEvalStepArgs(C.Structure):
                                    "flight", "remaining")]
 
 
+class D2DEvalBank(C.Structure):
+    """include/d2d_eval.h ``d2d_eval_bank``."""
+    _fields_ = [("n_policies", C.c_int32), ("pad", C.c_int32), ("params", _VP), ("env_policy", _VP)]
+
+
 class EvalError(RuntimeError):
     pass
 
@@ -42,16 +50,20 @@ class EvalError(RuntimeError):
 SIGNATURES = {
     "d2d_eval_abi_version": (C.c_int32, []),
     "d2d_eval_step": (C.c_int32, [C.POINTER(D2DEvalStepArgs), _VP]),
+    "d2d_eval_bank_version": (C.c_int32, []),
+    "d2d_eval_step_bank": (C.c_int32, [C.POINTER(D2DEvalStepArgs), C.POINTER(D2DEvalBank), _VP]),
 }
 
 _lib = None
 
 
 def bind(path: str) -> C.CDLL:
-    """The library at ``path`` with its signatures set and its ABI version checked."""
+    """The library at ``path`` with its signatures set and its ABI and bank versions checked."""
     from . import _native
 
-    return _native.bind(path, SIGNATURES, "d2d_eval_abi_version", ABI_VERSION, EvalError)
+    lib = _native.bind(path, SIGNATURES, "d2d_eval_abi_version", ABI_VERSION, EvalError)
+    _native.check_version(lib, path, "d2d_eval_bank_version", BANK_VERSION, EvalError, None)
+    return lib
 
 
 def load() -> C.CDLL:
@@ -72,6 +84,12 @@ def _step(lib, args: D2DEvalStepArgs, stream: int) -> None:
         raise EvalError(f"d2d_eval_step: hipError {rc}" + (" (contradictory arguments)" if rc == 1 else ""))
 
 
+def _step_bank(lib, args: D2DEvalStepArgs, bank: D2DEvalBank, stream: int) -> None:
+    rc = lib.d2d_eval_step_bank(C.byref(args), C.byref(bank), stream)
+    if rc:
+        raise EvalError(f"d2d_eval_step_bank: hipError {rc}" + (" (contradictory arguments)" if rc == 1 else ""))
+
+
 def _actor_critic(policy):
     """The ``ActorCritic`` behind a ``ppo.PPO``, or the policy itself."""
     return policy.policy if hasattr(policy, "collect_rollouts") else policy
@@ -89,8 +107,7 @@ def actor_tensors(policy, device) -> tuple:
     else:
         raise TypeError(f"cannot evaluate a {type(policy).__name__}: expected ActorCritic, MlpActor or PPO")
     out = tuple(t.detach().to(device=device, dtype=torch.float32).contiguous() for t in ts)
-    shapes = ((64, 27), (64,), (64, 64), (64,), (2, 64), (2,), (2,))
-    if tuple(tuple(t.shape) for t in out) != shapes:
+    if tuple(tuple(t.shape) for t in out) != _BANK_SHAPES:
         raise ValueError("the evaluation step runs SB3's MlpPolicy actor 27-64-64-2 only")
     return out
 
@@ -114,6 +131,13 @@ def act(policy, obs: torch.Tensor, *, deterministic: bool = False, seed: int = 0
     """The act half alone on a HIP tensor ``obs`` [n, 27]: clip(mean + exp(log_std) z, -1, 1) [n, 2],
     with z = 0 (``deterministic``), ``noise`` [n, 2], or the Philox draw of (seed, env_id_base + i, t).
     ``return_noise``: also the z that was used."""
+    return _act(obs, lambda dev: actor_tensors(policy, dev), None, None, deterministic, seed, t, env_id_base, noise,
+                return_noise)
+
+
+def _act(obs, weights, bank, env_policy, deterministic, seed, t, env_id_base, noise, return_noise):
+    """``act`` under one actor (``weights(device)`` -> its seven tensors) or under a ``PolicyBank``
+    with its env -> policy map."""
     if not obs.is_cuda:
         raise ValueError("evaluate.act runs on a HIP device; use the policy's torch forward on the CPU")
     lib = load()
@@ -123,12 +147,16 @@ def act(policy, obs: torch.Tensor, *, deterministic: bool = False, seed: int = 0
     if x.dim() != 2 or x.shape[1] != abi.OBS_DIM:
         raise ValueError("obs must be [n, 27]")
     out = torch.empty(n, abi.ACT_DIM, dtype=torch.float32, device=dev)
+    if bank is not None:
+        bank = bank.to(dev)
+        ep = torch.from_numpy(check_env_policy(env_policy, n, bank.n_policies)).to(dev)
     if n == 0:
         return (out, out.clone()) if return_noise else out
-    ws = actor_tensors(policy, dev)
     a = D2DEvalStepArgs(n=n, t=int(t), info_dim=abi.INFO_DIM, act=1, env_id_base=int(env_id_base),
                         seed=int(seed) & (2 ** 64 - 1), obs=x.data_ptr(), act_env=out.data_ptr())
-    _weights_into(a, ws)
+    if bank is None:
+        ws = weights(dev)
+        _weights_into(a, ws)
     z = None
     if deterministic:
         a.noise_mode = NOISE_NONE
@@ -144,7 +172,11 @@ def act(policy, obs: torch.Tensor, *, deterministic: bool = False, seed: int = 0
         zo = torch.zeros(n, abi.ACT_DIM, dtype=torch.float32, device=dev)
         a.noise_out = zo.data_ptr()
     with torch.cuda.device(dev):
-        _step(lib, a, torch.cuda.current_stream(dev).cuda_stream)
+        stream = torch.cuda.current_stream(dev).cuda_stream
+        if bank is None:
+            _step(lib, a, stream)
+        else:
+            _step_bank(lib, a, bank.c_bank(ep), stream)
     return (out, zo) if return_noise else out
 
 
@@ -234,6 +266,22 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
         return harness.run_first_episodes(venv, as_mlp_actor(policy), deterministic=deterministic, seed=seed,
                                           max_steps=max_steps, n_obstacles=n_obstacles, flight_paths=flight_paths,
                                           check_every=check_every)
+    fin, rows_np, xy_np, nobs, actions, _ = _fly(venv, actor_tensors(policy, venv.device), None, deterministic, seed,
+                                                 max_steps, n_obstacles, flight_paths, check_every, noise, keep_actions)
+    out = _records(venv, fin, rows_np, xy_np, nobs)
+    if keep_actions:
+        out["actions"] = actions
+    return out
+
+
+def _fly(venv, ws, bank, deterministic, seed, max_steps, n_obstacles, flight_paths, check_every, noise, keep_actions,
+         extra=()):
+    """The closed loop of ``evaluate_policy`` on a HIP batch under one actor (``ws``, its seven tensors)
+    or a policy bank (``bank``: a ``D2DEvalBank`` whose tensors the caller keeps alive): the recorder's
+    arrays over the whole batch in global env order (gathered over the ranks, and with them the
+    per-env arrays in ``extra``), the obstacle count, and this rank's actions [steps, n, 2]."""
+    from . import harness
+
     if not venv.with_info:
         raise ValueError("evaluate_policy needs the env's info rows (with_info=True)")
     lib = load()
@@ -250,7 +298,7 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
     cap = int(max_steps) if max_steps is not None else int(venv.kwargs["n_steps"]) + 1
     # (info_dicts ignores it; a fresh-curriculum batch has no static scenario to count obstacles of)
     nobs = n_obstacles if n_obstacles is not None else (len(venv.scenarios[0].circles) if venv.scenarios else 0)
-    ws = actor_tensors(policy, dev)
+    step = (lambda a, st: _step(lib, a, st)) if bank is None else (lambda a, st: _step_bank(lib, a, bank, st))
     with torch.cuda.device(dev):
         obs = venv.reset(seed=seed)
         finished = torch.zeros(n, dtype=torch.uint8, device=dev)
@@ -260,7 +308,8 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
         pos = torch.full((cap, n, 2), float("nan"), dtype=torch.float32, device=dev) if flight_paths else None
         a = D2DEvalStepArgs(n=n, info_dim=abi.INFO_DIM, flight_cap=cap, env_id_base=base,
                             seed=int(seed) & (2 ** 64 - 1), act_env=act_env.data_ptr())
-        _weights_into(a, ws)
+        if bank is None:
+            _weights_into(a, ws)
         gen = z = None
         if deterministic:
             a.noise_mode = NOISE_NONE
@@ -278,7 +327,7 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
                 z = torch.randn((n_total, 2), device=dev, dtype=torch.float32, generator=gen)[offset:offset + n]
                 z = z.contiguous()
                 a.noise = z.data_ptr()
-            _step(lib, a, stream)
+            step(a, stream)
             if keep_actions and not last:
                 actions.append(act_env.clone())
             if last or (t and t % check_every == 0 and int(remaining.item()) == 0):
@@ -293,21 +342,248 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
         fin = finished.cpu().numpy().astype(bool)
         rows_np = rows.cpu().numpy()
         xy_np = pos.cpu().numpy() if pos is not None else None
+    extra = tuple(np.asarray(e) for e in extra)
     if world > 1:
         parts = [None] * world
-        dist.all_gather_object(parts, (offset, fin, rows_np, xy_np))
+        dist.all_gather_object(parts, (offset, fin, rows_np, xy_np, extra))
         parts.sort(key=lambda p: p[0])
         fin = np.concatenate([p[1] for p in parts])
         rows_np = np.concatenate([p[2] for p in parts])
         if xy_np is not None:
             T = max(p[3].shape[0] for p in parts)
             xy_np = np.concatenate([p[3][:T] for p in parts], 1)
-    out = _records(venv, fin, rows_np, xy_np, nobs)
+        extra = tuple(np.concatenate([p[4][k] for p in parts]) for k in range(len(extra)))
     if keep_actions:
         # the call that found every env finished had already written the next step's actions: drop them
-        out["actions"] = (torch.stack(actions[:steps]) if steps else torch.empty(0, n, 2, device=dev)).cpu().numpy()
-    return out
+        actions = (torch.stack(actions[:steps]) if steps else torch.empty(0, n, 2, device=dev)).cpu().numpy()
+    return fin, rows_np, xy_np, nobs, actions, extra
+
+
+# ---------------------------------------------------------------- the policy bank: many agents in one batch
+class PolicyBank:
+    """P actors packed for ``d2d_eval_step_bank``: ``params`` float32 [P, 6084], policy p's row holding
+    W1, b1, W2, b2, W3, b3, log_std in the header's order.  ``policies``: each an ``ActorCritic``, a
+    ``harness.MlpActor``, a ``ppo.PPO`` or the path of an agent zip (``ActorCritic.from_sb3_zip``);
+    ``names``: one per policy, unique (default: a zip's file name without its extension, else
+    ``policy_<p>``); ``device``: default the current HIP device, the CPU without one."""
+
+    def __init__(self, policies, names=None, device=None):
+        from .policy import ActorCritic
+
+        policies = list(policies)
+        if not policies:
+            raise ValueError("a policy bank needs at least one policy")
+        if device is None:
+            device = torch.device("cuda", torch.cuda.current_device()) if torch.cuda.is_available() else "cpu"
+        if names is None:
+            names = [os.path.splitext(os.path.basename(os.fspath(p)))[0] if isinstance(p, (str, os.PathLike))
+                     else f"policy_{k}" for k, p in enumerate(policies)]
+        self.names = [str(s) for s in names]
+        if len(self.names) != len(policies) or len(set(self.names)) != len(policies):
+            raise ValueError("names must be one unique name per policy")
+        rows = []
+        for p in policies:
+            if isinstance(p, (str, os.PathLike)):
+                p = ActorCritic.from_sb3_zip(os.fspath(p))
+            rows.append(torch.cat([t.reshape(-1) for t in actor_tensors(p, "cpu")]))
+        self.params = torch.stack(rows).to(device).contiguous()
+        assert self.params.shape[1] == BANK_STRIDE
+
+    @property
+    def n_policies(self) -> int:
+        return int(self.params.shape[0])
+
+    @property
+    def device(self) -> torch.device:
+        return self.params.device
+
+    def __len__(self) -> int:
+        return self.n_policies
+
+    def to(self, device) -> "PolicyBank":
+        """This bank on ``device`` (itself when it already is there)."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device == self.params.device:
+            return self
+        other = object.__new__(PolicyBank)
+        other.names, other.params = self.names, self.params.to(device)
+        return other
+
+    def tensors(self, p: int) -> tuple:
+        """(W1, b1, W2, b2, W3, b3, log_std) of policy ``p``: views of its row of ``params``."""
+        row, out, o = self.params[p], [], 0
+        for shape in _BANK_SHAPES:
+            k = int(np.prod(shape))
+            out.append(row[o:o + k].view(shape))
+            o += k
+        return tuple(out)
+
+    def mlp_actor(self, p: int, batch_invariant: bool = False):
+        """Policy ``p`` as a ``harness.MlpActor`` (a copy, on the CPU)."""
+        from .harness import MlpActor
+
+        keys = ("mlp_extractor_policy_net_0_weight", "mlp_extractor_policy_net_0_bias",
+                "mlp_extractor_policy_net_2_weight", "mlp_extractor_policy_net_2_bias", "action_net_weight",
+                "action_net_bias", "log_std")
+        return MlpActor({k: t.cpu().numpy() for k, t in zip(keys, self.tensors(p))}, batch_invariant=batch_invariant)
+
+    def c_bank(self, env_policy: torch.Tensor) -> D2DEvalBank:
+        """The ABI record over ``params`` and an int32 map on the bank's device (the caller keeps both alive)."""
+        assert env_policy.dtype == torch.int32 and env_policy.device == self.params.device and env_policy.is_contiguous()
+        return D2DEvalBank(n_policies=self.n_policies, params=self.params.data_ptr(), env_policy=env_policy.data_ptr())
+
+
+def _as_bank(bank) -> PolicyBank:
+    return bank if isinstance(bank, PolicyBank) else PolicyBank(bank)
+
+
+def check_env_policy(env_policy, n: int, n_policies: int) -> np.ndarray:
+    """``env_policy`` as a contiguous int32 array [n] with every value in [0, P), or a ``ValueError``:
+    the library skips an env whose id is outside the bank, so such a map is refused on the host."""
+    ep = env_policy.detach().cpu().numpy() if isinstance(env_policy, torch.Tensor) else np.asarray(env_policy)
+    if ep.dtype.kind not in "iu":
+        raise ValueError("env_policy must be an integer array")
+    if ep.shape != (n,):
+        raise ValueError(f"env_policy must have shape [{n}]")
+    if n and (int(ep.min()) < 0 or int(ep.max()) >= n_policies):
+        raise ValueError(f"env_policy values must lie in [0, {n_policies})")
+    return np.ascontiguousarray(ep, dtype=np.int32)
+
+
+@torch.no_grad()
+def act_bank(bank, obs: torch.Tensor, env_policy, *, deterministic: bool = False, seed: int = 0, t: int = 0,
+             env_id_base: int = 0, noise: torch.Tensor | None = None, return_noise: bool = False):
+    """``act`` with env i under policy ``env_policy[i]`` of ``bank``, one launch: row i is, bit for bit,
+    row i of ``act(policy env_policy[i], obs, ...)``."""
+    return _act(obs, None, _as_bank(bank), env_policy, deterministic, seed, t, env_id_base, noise, return_noise)
+
+
+class BankActor(torch.nn.Module):
+    """The bank for the torch loop (``harness.run_first_episodes``): ``act`` applies each policy's
+    ``MlpActor`` to that policy's rows and scatters the results back.  The actors are
+    ``batch_invariant``, so a row's action does not depend on how many rows share its policy."""
+
+    def __init__(self, bank: PolicyBank, env_policy):
+        super().__init__()
+        self.actors = torch.nn.ModuleList(bank.mlp_actor(p, batch_invariant=True) for p in range(bank.n_policies))
+        ep = torch.from_numpy(check_env_policy(env_policy, len(env_policy), bank.n_policies)).long()
+        self.register_buffer("env_policy", ep)
+
+    @torch.no_grad()
+    def act(self, obs: torch.Tensor, deterministic: bool = False, generator: torch.Generator | None = None,
+            noise: torch.Tensor | None = None):
+        if not deterministic and noise is None:
+            noise = torch.randn((obs.shape[0], 2), device=obs.device, dtype=obs.dtype, generator=generator)
+        out = torch.empty(obs.shape[0], 2, dtype=obs.dtype, device=obs.device)
+        for p, actor in enumerate(self.actors):
+            idx = torch.nonzero(self.env_policy == p).squeeze(1)
+            if len(idx):
+                out[idx] = actor.act(obs[idx], deterministic=deterministic, noise=None if deterministic else noise[idx])
+        return out
+
+
+@torch.no_grad()
+def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool = False, seed: int = 0,
+                      max_steps: int | None = None, n_obstacles: int | None = None, flight_paths: bool = False,
+                      check_every: int = 16, noise: str = "philox", keep_actions: bool = False):
+    """``evaluate_policy`` for a batch whose envs belong to different agents: env i flies under policy
+    ``env_policy[i]`` of ``bank`` (a ``PolicyBank`` or a list of policies), one ``d2d_eval_step_bank``
+    per env step.  Returns one result dict per policy (a list), each what ``evaluate_policy`` returns,
+    built from that policy's envs in env order: ``flight_xy`` trimmed to their longest episode,
+    ``actions`` their columns.  ``split``: an int array [n] of labels (a scenario index, say); the
+    result is then a dict keyed (policy, label) over the pairs the batch holds.
+
+    Env i's episode is, bit for bit, the one ``evaluate_policy`` flies it under its policy alone in the
+    same batch: the actor is row-invariant across the bank, and noise and spawns are keyed by global
+    env id.  Under ``torch.distributed`` every rank passes its shard's slice of the map (and of
+    ``split``); the records are gathered in global env order and split afterwards.  A batch that is not
+    a HIP ``Drone2dVecEnv`` goes through ``harness.run_first_episodes`` under a ``BankActor``."""
+    from . import harness
+    from .env import Drone2dVecEnv
+
+    if noise not in ("philox", "torch"):
+        raise ValueError("noise must be 'philox' or 'torch'")
+    bank = _as_bank(bank)
+    n = int(venv.num_envs)
+    ep = check_env_policy(env_policy, n, bank.n_policies)
+    labels = None
+    if split is not None:
+        labels = split.detach().cpu().numpy() if isinstance(split, torch.Tensor) else np.asarray(split)
+        if labels.dtype.kind not in "iu" or labels.shape != (n,):
+            raise ValueError(f"split must be an integer array of shape [{n}]")
+    extra = (ep,) if labels is None else (ep, labels)
+    actions = None
+    if not isinstance(venv, Drone2dVecEnv):
+        if keep_actions:
+            raise ValueError("keep_actions needs a HIP batch")
+        raw = harness.run_first_episodes(venv, BankActor(bank, ep), deterministic=deterministic, seed=seed,
+                                         max_steps=max_steps, n_obstacles=n_obstacles, flight_paths=flight_paths,
+                                         check_every=check_every, records=False, extra=extra)
+        fin, rows_np, xy_np, nobs, extra = raw["finished"], raw["rows"], raw["xy"], raw["n_obstacles"], raw["extra"]
+    else:
+        bank = bank.to(venv.device)
+        ep_dev = torch.from_numpy(ep).to(venv.device)
+        fin, rows_np, xy_np, nobs, actions, extra = _fly(venv, None, bank.c_bank(ep_dev), deterministic, seed, max_steps,
+                                                         n_obstacles, flight_paths, check_every, noise, keep_actions,
+                                                         extra)
+    g_ep, g_labels = extra[0], (extra[1] if labels is not None else None)
+
+    def subset(mask, local_mask):
+        idx = np.flatnonzero(mask)
+        out = _records(venv, fin[idx], rows_np[idx], xy_np[:, idx] if xy_np is not None else None, nobs)
+        if keep_actions:
+            out["actions"] = actions[:, np.flatnonzero(local_mask)]
+        return out
+
+    if labels is None:
+        return [subset(g_ep == p, ep == p) for p in range(bank.n_policies)]
+    pairs = sorted(set(zip(g_ep.tolist(), g_labels.tolist())))
+    return {(p, s): subset((g_ep == p) & (g_labels == s), (ep == p) & (labels == s)) for p, s in pairs}
+
+
+def sweep_layout(n_policies: int, n_scenarios: int, runs: int) -> tuple:
+    """(env_policy, env_scenario), int32 [P S R] each, of a sweep batch: policy-major, then scenario,
+    then run.  A policy's envs are contiguous, so at most one 64-env chunk per policy boundary holds
+    two policies."""
+    P, S, R = int(n_policies), int(n_scenarios), int(runs)
+    if P < 1 or S < 1 or R < 1:
+        raise ValueError("sweep_layout needs at least one policy, one scenario and one run")
+    return (np.repeat(np.arange(P, dtype=np.int32), S * R),
+            np.tile(np.repeat(np.arange(S, dtype=np.int32), R), P))
+
+
+def sweep(bank, scenarios, runs: int, *, seed: int = 0, deterministic: bool = False, flight_paths: bool = False,
+          env_kwargs: dict | None = None) -> dict:
+    """Every agent of ``bank`` on every scenario, ``runs`` first episodes each, as one batch of
+    P S R envs (``sweep_layout``) in one closed loop: {agent name: {scenario name: result dict}}.
+    ``scenarios``: names of static scenarios or ``Scenario`` objects (a curriculum stage is refused:
+    pass a fresh-curriculum batch to ``evaluate_policies``); ``env_kwargs``: default ``ENV_TEST_CONFIG``.
+    Every (agent, scenario, run) is an env of its own global id, so its spawn and noise draws are its own."""
+    from .config import CURRICULUM_STAGES, ENV_TEST_CONFIG
+    from .env import Drone2dVecEnv, is_curriculum
+
+    bank = _as_bank(bank)
+    scenarios = [scenarios] if isinstance(scenarios, str) else list(scenarios)
+    kw = dict(ENV_TEST_CONFIG if env_kwargs is None else env_kwargs, scenario=scenarios)
+    if not scenarios or any(isinstance(s, str) and s in CURRICULUM_STAGES for s in scenarios) or is_curriculum(kw):
+        raise ValueError("sweep takes static scenarios (names or Scenario objects), at least one")
+    names = [s if isinstance(s, str) else s.name for s in scenarios]
+    if len(set(names)) != len(names):
+        raise ValueError("sweep: scenario names must be unique")
+    ep, es = sweep_layout(bank.n_policies, len(scenarios), runs)
+    if not bank.device.type == "cuda":
+        raise ValueError("sweep runs on a HIP device: build the bank there")
+    venv = Drone2dVecEnv(len(ep), device=bank.device, seed=seed, with_info=True, env_scenario=es, **kw)
+    try:
+        res = evaluate_policies(venv, bank, ep, split=es, deterministic=deterministic, seed=seed,
+                                flight_paths=flight_paths)
+    finally:
+        venv.close()
+    return {bank.names[p]: {names[s]: res[(p, s)] for s in range(len(names))} for p in range(bank.n_policies)}
 
 
 __all__ = ["evaluate_policy", "act", "actor_tensors", "as_mlp_actor", "philox_noise_host", "load", "bind", "EvalError",
-           "D2DEvalStepArgs"]
+           "D2DEvalStepArgs", "D2DEvalBank", "PolicyBank", "BankActor", "act_bank", "evaluate_policies", "sweep_layout",
+           "sweep", "check_env_policy"]

@@ -96,7 +96,7 @@ def _dist_world():
 def run_first_episodes(venv, policy: MlpActor, *, deterministic: bool = False, seed: int = 0,
                        max_steps: int | None = None, n_obstacles: int | None = None,
                        flight_paths: bool = False, check_every: int = 16, gather: bool = True,
-                       policy_device=None) -> dict:
+                       policy_device=None, records: bool = True, extra=()) -> dict:
     """Step ``venv`` (with info rows) under ``policy`` until every env has finished its first
     episode; per-episode records as the reference's test loop keeps them (main.py:273-281).
 
@@ -123,7 +123,12 @@ def run_first_episodes(venv, policy: MlpActor, *, deterministic: bool = False, s
 
     ``policy_device``: where the policy and its noise run (default: the env's device).  The
     parity tests pass "cpu" for the HIP batch and the CPU oracle alike, so both see the same
-    actions for the same observations (a GPU tanh or N(0, 1) stream is not the CPU one)."""
+    actions for the same observations (a GPU tanh or N(0, 1) stream is not the CPU one).
+
+    ``records=False``: instead of the result dict, what it is built from, over the whole (gathered)
+    batch in global env order -- ``finished`` bool [n], ``rows`` [n, INFO_DIM], ``xy`` [cap, n, 2] or
+    None, ``n_obstacles``, and ``extra``: the caller's per-env arrays, gathered alike -- for a caller
+    that splits the batch into several result sets (``evaluate.evaluate_policies``)."""
     dev = venv.device
     pdev = torch.device(policy_device) if policy_device is not None else dev
     dist, rank, world = _dist_world()
@@ -160,15 +165,19 @@ def run_first_episodes(venv, policy: MlpActor, *, deterministic: bool = False, s
     fin = finished.cpu().numpy()
     rows_np = rows.cpu().numpy()
     xy_np = pos.cpu().numpy() if pos is not None else None
+    extra = tuple(np.asarray(e) for e in extra)
     if world > 1 and gather:
         parts = [None] * world
-        dist.all_gather_object(parts, (offset, fin, rows_np, xy_np))
+        dist.all_gather_object(parts, (offset, fin, rows_np, xy_np, extra))
         parts.sort(key=lambda p: p[0])
         fin = np.concatenate([p[1] for p in parts])
         rows_np = np.concatenate([p[2] for p in parts])
         if xy_np is not None:
             T = max(p[3].shape[0] for p in parts)
             xy_np = np.concatenate([p[3][:T] for p in parts], 1)
+        extra = tuple(np.concatenate([p[4][k] for p in parts]) for k in range(len(extra)))
+    if not records:
+        return {"finished": fin, "rows": rows_np, "xy": xy_np, "n_obstacles": nobs, "extra": extra}
     idx = np.flatnonzero(fin)
     recs = [info_dicts(r, nobs) for r in rows_np[idx]]
     out = {
@@ -303,6 +312,42 @@ def write_results(m: dict, out_dir: str, scenario: str, agent_nr: str, agent_pat
     return s
 
 
+SELECTION_COLUMNS = ("agent", "scenario", "episodes", "success_rate", "collision_rate", "average_ape",
+                     "average_flight_time")
+
+
+def selection_table(results: dict) -> list:
+    """The agent-by-scenario table a checkpoint is picked from (the reference keeps it by hand in
+    barplots.py): one row (agent, scenario, episodes, success rate, collision rate, average APE,
+    average flight time) per pair of ``results`` = {agent: {scenario: result dict}} (``evaluate.sweep``),
+    in its order; the numbers are ``summary``'s (NaN averages for a pair with no finished episode)."""
+    rows = []
+    for agent, per_scn in results.items():
+        for scn, m in per_scn.items():
+            s = summary(m)
+            rows.append((agent, scn, s["Successes"] + s["Fails"], s["Success rate"], s["Collision rate"],
+                         s["Average APE"], s["Average flight time"]))
+    return rows
+
+
+def write_selection(results: dict, out_dir: str) -> list:
+    """``selection_table(results)`` as ``selection.csv`` (a header line, floats by ``repr``) and
+    ``selection.json`` (a list of objects; NaN written as null) under ``out_dir``; returns the rows."""
+    import csv
+
+    rows = selection_table(results)
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "selection.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(SELECTION_COLUMNS)
+        for r in rows:
+            w.writerow([repr(float(v)) if isinstance(v, float) else v for v in r])
+    with open(os.path.join(out_dir, "selection.json"), "w") as f:
+        json.dump([{k: (None if isinstance(v, float) and v != v else v) for k, v in zip(SELECTION_COLUMNS, r)}
+                   for r in rows], f, indent=1)
+    return rows
+
+
 def save_gif(frames, path: str, fps: int = 60) -> None:
     """Frames [T, H, W, 3] as an animated GIF (the reference's per-scenario GIF, main.py:283-300);
     needs Pillow and raises ImportError without it."""
@@ -312,4 +357,5 @@ def save_gif(frames, path: str, fps: int = 60) -> None:
 
 
 __all__ = ["MlpActor", "run_first_episodes", "flight_path_lists", "summary", "write_results",
-           "write_results_rank0", "plot_flight_paths", "plot_inputs", "flight_path_colours", "save_gif"]
+           "write_results_rank0", "plot_flight_paths", "plot_inputs", "flight_path_colours", "save_gif",
+           "selection_table", "write_selection", "SELECTION_COLUMNS"]

@@ -81,6 +81,33 @@ typedef struct d2d_eval_step_args {
  * u_k = ((w_k >> 8) + 0.5) * 2^-24 in float32; r = sqrtf(-2 logf(u0)); z = (r cosf(2 pi u1), r sinf(2 pi u1)). */
 int32_t d2d_eval_step(const d2d_eval_step_args* args, void* stream);
 
+/* The policy bank: one launch acts for envs that belong to different agents (a sweep of P agents x
+ * S scenarios x R runs as one batch; drone2d_amd.evaluate.evaluate_policies).  Additive: the functions
+ * above and D2D_EVAL_ABI_VERSION are unchanged; the bank carries a version of its own. */
+#define D2D_EVAL_BANK_VERSION 1
+#define D2D_EVAL_BANK_STRIDE  6084   /* floats per policy, in this order: W1 [64][27], b1 [64], W2 [64][64],
+                                        b2 [64], W3 [2][64], b3 [2], log_std [2] */
+typedef struct d2d_eval_bank {
+    int32_t n_policies;          /* P >= 1 */
+    int32_t pad;
+    const float* params;         /* [P][D2D_EVAL_BANK_STRIDE] */
+    const int32_t* env_policy;   /* [n]: the policy of env i */
+} d2d_eval_bank;
+int32_t d2d_eval_bank_version(void);
+
+/* d2d_eval_step with one difference: env i's actor and log_std are those of policy env_policy[i].
+ * args->w1 ... args->log_std must all be NULL; the record half, the noise modes, noise_out, env_id_base
+ * and t are d2d_eval_step's.  One launch, stream-ordered, no synchronisation, no allocation.
+ *
+ * Row invariance extends to the bank: env i's action is, bit for bit, the action d2d_eval_step gives
+ * the same observation row under policy env_policy[i] alone, whatever policies its neighbours have.
+ * The map is arbitrary: a workgroup handles a 64-env chunk once per distinct policy present, in
+ * ascending policy order, with that policy's weights staged, and keeps only that policy's rows.
+ * An env whose id is outside [0, P) is skipped: the id never indexes the bank and act_env[i] is not
+ * written.  hipErrorInvalidValue (nothing launched): bank NULL, P < 1, any of w1 ... log_std non-NULL,
+ * with act != 0 a NULL params or env_policy (act == 0 reads neither), or what d2d_eval_step rejects. */
+int32_t d2d_eval_step_bank(const d2d_eval_step_args* args, const d2d_eval_bank* bank, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
