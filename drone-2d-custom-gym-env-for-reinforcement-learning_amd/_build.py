@@ -40,6 +40,10 @@ EVAL_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_eval.so")
 MONITOR_SRC = os.path.join(PKG_DIR, "csrc", "monitor", "d2d_monitor.hip")
 MONITOR_HDRS = [os.path.join(REPO, "include", "d2d_monitor.h"), os.path.join(REPO, "include", "drone2d.h")]
 MONITOR_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_monitor.so")
+# reward normalisation (include/d2d_norm.h), a library of its own under csrc/norm/
+NORM_SRC = os.path.join(PKG_DIR, "csrc", "norm", "d2d_norm.hip")
+NORM_HDRS = [os.path.join(REPO, "include", "d2d_norm.h")]
+NORM_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_norm.so")
 
 # -ffp-contract=off: the kernels follow the reference's NumPy evaluation order (explicit fma() only
 # where NumPy/OpenBLAS fuses); no fast-math: IEEE inf/NaN semantics are part of the contract.
@@ -114,11 +118,21 @@ def build_monitor(force: bool = False, verbose: bool = False) -> str:
     return MONITOR_OUT
 
 
+def build_norm(force: bool = False, verbose: bool = False) -> str:
+    """Reward normalisation (libd2d_norm.so), with the env's flags (-ffp-contract=off: its float64
+    expressions and sums are plain IEEE operations in the order include/d2d_norm.h states, which the
+    host twin repeats).  Compiled by ``build()`` or by the first ``RewardNormalizer`` on a HIP device
+    that finds it missing."""
+    if force or needs_build(NORM_OUT, NORM_SRC, NORM_HDRS):
+        _compile(NORM_SRC, NORM_OUT, verbose)
+    return NORM_OUT
+
+
 def build(force: bool = False, verbose: bool = False, exact: bool = False) -> str:
     """The in-tree libraries: the env (libdrone2d_hip.so: every mode, one scenario layout), the PPO
     update kernels (libd2d_ppo.so), the renderer (libd2d_render.so), the evaluation step
-    (libd2d_eval.so), the episode monitor (libd2d_monitor.so) and, with ``exact``, the env's
-    exact-trig build."""
+    (libd2d_eval.so), the episode monitor (libd2d_monitor.so), reward normalisation (libd2d_norm.so)
+    and, with ``exact``, the env's exact-trig build."""
     stale = os.path.join(PKG_DIR, "_lib", "libdrone2d_hip_rm.so")  # rounds 1-3's second layout build
     if os.path.exists(stale):
         os.remove(stale)
@@ -131,4 +145,5 @@ def build(force: bool = False, verbose: bool = False, exact: bool = False) -> st
     build_render(force, verbose)
     build_eval(force, verbose)
     build_monitor(force, verbose)
+    build_norm(force, verbose)
     return OUT

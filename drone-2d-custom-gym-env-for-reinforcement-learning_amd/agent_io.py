@@ -12,7 +12,7 @@ import numpy as np
 import torch
 
 AGENT_FORMAT_VERSION = 1
-AGENT_MEMBERS = ("data.json", "policy.pth", "train_state.pth", "env_state.pth")
+AGENT_MEMBERS = ("data.json", "policy.pth", "train_state.pth", "env_state.pth", "reward_norm.pth")
 
 
 def _zip_tensors(z: zipfile.ZipFile, name: str) -> dict:
@@ -53,10 +53,11 @@ def write_agent(path: str, data: dict, members: dict) -> str:
 
 
 def read_agent(path: str) -> tuple:
-    """(``data.json``, {member: tensors}) of an agent file of this format version (``env_state.pth`` if it has one)."""
+    """(``data.json``, {member: tensors}) of an agent file of this format version (``env_state.pth`` and
+    ``reward_norm.pth`` if it has them)."""
     with zipfile.ZipFile(path) as z:
         data = json.loads(z.read("data.json"))
         if data.get("format_version") != AGENT_FORMAT_VERSION:
             raise ValueError(f"{path}: agent format {data.get('format_version')}, expected {AGENT_FORMAT_VERSION}")
-        names = ["policy.pth", "train_state.pth"] + [n for n in ("env_state.pth",) if n in z.namelist()]
+        names = ["policy.pth", "train_state.pth"] + [n for n in ("env_state.pth", "reward_norm.pth") if n in z.namelist()]
         return data, {n: _zip_tensors(z, n) for n in names}

@@ -19,6 +19,9 @@ this module restates the parts of SB3 2.1 that a training run executes, in the s
   ``approx_kl`` and the ``target_kl`` early stop, read from and decided in a device-resident
   ``ControlBlock`` so that they work inside the captured update (DESIGN.md "PPO control").  One
   minibatch step is a stepper's (ppo_step.py: ``ManualStep``, or ``AutogradStep`` for ``manual=False``).
+* ``PPOConfig.norm_reward`` (SB3 ``VecNormalize(norm_obs=False, norm_reward=True)``): the rollout records
+  rewards divided by the running standard deviation of the discounted returns (normalize.py,
+  libd2d_norm.so; DESIGN.md "Reward normalisation"); episode statistics and logs stay raw.
 
 At 65 536 envs a 2 048-step rollout would hold 134 M transitions, so GPU-scale runs shorten
 n_steps and enlarge batch_size (``PPOConfig.gpu_defaults``); the update rule is unchanged.  With
@@ -68,6 +71,12 @@ class PPOConfig:
     clip_range_end: float | None = None
     clip_range_vf: float | None = None      # SB3 clip_range_vf: the value prediction clipped around old_values
     target_kl: float | None = None          # SB3 target_kl; float("inf"): never stops, approx_kl logged only
+    # Reward normalisation (normalize.py, include/d2d_norm.h): SB3's VecNormalize(norm_obs=False,
+    # norm_reward=True, gamma=gamma, clip_reward=clip_reward, epsilon=norm_epsilon) inside the rollout.
+    # An agent file carries these three keys only when norm_reward is on (NORM_KEYS).
+    norm_reward: bool = False
+    clip_reward: float = 10.0
+    norm_epsilon: float = 1e-8
 
     def __post_init__(self):
         for name in ("learning_rate", "clip_range"):
@@ -95,6 +104,9 @@ class PPOConfig:
     def gpu_defaults(cls, **over) -> "PPOConfig":
         """Short rollouts over many envs (65 536 x 16 = 1 M samples per update), big minibatches."""
         return cls(**dict(dict(n_steps=16, batch_size=32768), **over))
+
+
+NORM_KEYS = ("norm_reward", "clip_reward", "norm_epsilon")
 
 
 @dataclass
@@ -140,6 +152,10 @@ class PPO:
         self.policy = (policy or ActorCritic()).to(self.device)
         self.world = dist.get_world_size() if dist.is_available() and dist.is_initialized() else 1
         self.use_graph = bool(self.cfg.graph and self.device.type == "cuda" and self.world == 1)
+        if self.cfg.norm_reward and self.world > 1:
+            raise ValueError("norm_reward=True with more than one rank: every rank would keep the running statistics "
+                             "of its own env shard and scale its rewards differently, and an all-reduced rms is not "
+                             "built")
         if self.world > 1:
             # one policy on every rank: rank 0's initial parameters; each rank its own noise stream
             for p in self.policy.parameters():
@@ -183,6 +199,12 @@ class PPO:
         self._predict_t = 0      # predict()'s call counter: the Philox step index of its noise
         self._predict_gen = None
         self.monitor = None      # an EpisodeMonitor (set_monitor / learn(monitor=...)); None: off
+        self.normalizer = None   # a RewardNormalizer (cfg.norm_reward); None: the rollout records raw rewards
+        if self.cfg.norm_reward:
+            from .normalize import RewardNormalizer
+
+            self.normalizer = RewardNormalizer(venv, self.cfg.gamma, self.cfg.clip_reward, self.cfg.norm_epsilon,
+                                               device=getattr(venv, "device", self.device))
 
     # ------------------------------------------------------------------ rollout
     def _alloc_rollout(self):
@@ -244,6 +266,8 @@ class PPO:
         obs = self.venv.reset()
         if self.monitor is not None:
             self.monitor.reset()
+        if self.normalizer is not None:
+            self.normalizer.reset()  # the discounted returns start over; the running statistics stay
         return obs
 
     @torch.no_grad()
@@ -275,6 +299,8 @@ class PPO:
                 obs, rew, term, trunc, info = self.venv.step(R["act_env"])
                 if self.monitor is not None:
                     self.monitor.step(term, trunc, info)
+                if self.normalizer is not None:  # (the monitor and the episode statistics read info: raw)
+                    rew = self.normalizer.step(rew, term, trunc)
                 r.prev_rew, r.prev_term, r.prev_trunc, r.prev_info = ptr(rew), ptr(term), ptr(trunc), ptr(info)
         if self.monitor is not None:
             self.monitor.flush()
@@ -299,6 +325,9 @@ class PPO:
             new_obs, rew, term, trunc, info = self.venv.step(actions.clamp(-1.0, 1.0))
             if self.monitor is not None:
                 self.monitor.step(term, trunc, info)
+            if self.normalizer is not None:
+                # before the truncation bootstrap below, the order SB3's PPO gets around a VecNormalize
+                rew = self.normalizer.step(rew, term, trunc)
             rew = rew.to(dev).float()
             trunc = trunc.to(dev)
             done = term.to(dev) | trunc
@@ -364,18 +393,30 @@ class PPO:
             body()
             self._ro_warm = True
         self.num_timesteps += T * N
-        if self.monitor is None:
+        if self.monitor is None and self.normalizer is None:
             f, r = float(R["fin"]), float(R["ret"])
             return {"episodes": f, "mean_return": r / f if f else float("nan")}
-        # fin, ret, the explained variance and the flushed vector packed on the device and read with
-        # one copy, where fin and ret were read before
-        ev = self._explained_variance().to(torch.float64)
-        host = torch.cat([R["fin"].reshape(1), R["ret"].reshape(1), ev.reshape(1),
-                          self.monitor.out.to(self.device)]).cpu()
+        # fin, ret, the normaliser's variance, the explained variance and the flushed vector packed on the
+        # device and read with one copy, where fin and ret were read before
+        pack = [R["fin"].reshape(1), R["ret"].reshape(1)]
+        if self.normalizer is not None:
+            pack.append(self.normalizer.rms[1:2].to(self.device))
+        if self.monitor is not None:
+            pack += [self._explained_variance().to(torch.float64).reshape(1), self.monitor.out.to(self.device)]
+        host = torch.cat(pack).cpu()
         f, r = float(host[0]), float(host[1])
         out = {"episodes": f, "mean_return": r / f if f else float("nan")}
-        out.update({"monitor/" + k: v for k, v in self.monitor.scalars(host[3:]).items()})
-        out["train/explained_variance"] = float(host[2])
+        at = 2
+        if self.normalizer is not None:
+            var = float(host[at])
+            at += 1
+        if self.monitor is not None:
+            out.update({"monitor/" + k: v for k, v in self.monitor.scalars(host[at + 1:]).items()})
+            out["train/explained_variance"] = float(host[at])
+        if self.normalizer is not None:
+            # what a reward is divided by after this rollout, and the running variance of the returns
+            out["norm/reward_scale"] = math.sqrt(var + self.normalizer.epsilon) if var == var else float("nan")
+            out["norm/return_var"] = var
         return out
 
     @torch.no_grad()
@@ -572,13 +613,22 @@ class PPO:
         SB3's names), ``train_state.pth`` (Adam moments and step counter, the rollout noise generator,
         the shuffle counter, the rollout's carried observations and episode starts), ``env_state.pth``
         (``venv.state_dict()``, when the batch has one) and ``data.json`` (format version, PPOConfig,
-        num_timesteps, n_envs, seed).  Tensors and JSON only."""
+        num_timesteps, n_envs, seed).  With ``norm_reward`` also ``reward_norm.pth`` (the normaliser's
+        ``rms`` and ``ret``); without it the file has neither that member nor the config's NORM_KEYS, so
+        it is the file earlier versions wrote and read.  Tensors and JSON only."""
         if self.device.type == "cuda":
             torch.cuda.synchronize(self.device)
         members = {"policy.pth": _to_tensors(dict(self.policy.state_dict())), "train_state.pth": self._train_state()}
         if hasattr(self.venv, "state_dict"):
             members["env_state.pth"] = _to_tensors(self.venv.state_dict())
-        data = {"format_version": AGENT_FORMAT_VERSION, "config": dataclasses.asdict(self.cfg),
+        if self.normalizer is not None:
+            sd = self.normalizer.state_dict()
+            members["reward_norm.pth"] = {"rms": sd["rms"], "ret": sd["ret"]}
+        config = dataclasses.asdict(self.cfg)
+        if not self.cfg.norm_reward:
+            for k in NORM_KEYS:
+                del config[k]
+        data = {"format_version": AGENT_FORMAT_VERSION, "config": config,
                 "num_timesteps": int(self.num_timesteps), "n_envs": self.n_envs, "seed": self.seed}
         return write_agent(path, data, members)
 
@@ -604,6 +654,10 @@ class PPO:
         algo.gen.set_state(ts["gen"])
         algo._perm_ctr.copy_(ts["perm_ctr"])
         algo.num_timesteps = int(data["num_timesteps"])
+        if algo.normalizer is not None:
+            if "reward_norm.pth" not in members:
+                raise ValueError(f"{path}: saved with norm_reward but without reward_norm.pth")
+            algo.normalizer.load_state_dict(members["reward_norm.pth"])
         if restore_env and "env_state.pth" in members and hasattr(venv, "load_state_dict"):
             venv.load_state_dict(_to_arrays(members["env_state.pth"]))
         if "last_obs" in ts:

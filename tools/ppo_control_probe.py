@@ -2,14 +2,15 @@
 """The measurements of DESIGN.md "PPO control" (one MI355X; a record, the only bar is on `train`'s
 default path).
 
-    python tools/ppo_control_probe.py train [--parent-tree DIR [--parent-control]] [--runs 5] [--updates 30]
+    python tools/ppo_control_probe.py train [--parent-tree DIR [--parent-control]] [--norm-reward] [--runs 5] [--updates 30]
     python tools/ppo_control_probe.py stop  [--rounds 7]
 
 ``train``: DESIGN.md "Monitor"'s protocol -- ``tools/train_ppo.py``, 65 536 corridor envs, 30 updates, a
 fresh process per run, the median env-steps/s over the updates after the graph captures (update >= 3)
 -- for this tree's default path, this tree with ``--target-kl inf`` (the control path, never stopping)
 and, with ``--parent-tree``, the parent commit's built tree (``--parent-control``: that tree with
-``--target-kl inf`` as well), alternating in one call.
+``--target-kl inf`` as well), alternating in one call.  ``--norm-reward`` (DESIGN.md "Reward normalisation"):
+the control arm is replaced by this tree with ``--norm-reward``, and the rollout's seconds are kept too.
 ``stop``: one captured update of the headline configuration (320 minibatch steps) that runs in full
 against one that stops at its first minibatch (``target_kl = -1``), the same graph replayed.
 Results: ``profiles/ppo_control/<mode>_probe.json`` (``--out``).
@@ -25,7 +26,7 @@ import sys
 import time
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-ARMS = ("parent", "parent_control", "default", "control")
+ARMS = ("parent", "parent_control", "default", "control", "norm")
 
 
 def _train_run(tree: str, a, extra=()) -> dict:
@@ -38,7 +39,8 @@ def _train_run(tree: str, a, extra=()) -> dict:
     upd = [x for x in recs if "update" in x]
     steady = [x["env_steps_per_s"] for x in upd if x["update"] >= 3]
     out = {"whole_run": recs[-1]["env_steps_per_s_incl_learning"], "steady_median": statistics.median(steady),
-           "train_s_median": statistics.median(x["train_s"] for x in upd if x["update"] >= 3)}
+           "train_s_median": statistics.median(x["train_s"] for x in upd if x["update"] >= 3),
+           "rollout_s_median": statistics.median(x["rollout_s"] for x in upd if x["update"] >= 3)}
     if "approx_kl" in upd[-1]:
         out["last_approx_kl"], out["last_n_minibatches"] = upd[-1]["approx_kl"], upd[-1]["n_minibatches"]
     return out
@@ -46,7 +48,7 @@ def _train_run(tree: str, a, extra=()) -> dict:
 
 def train_probe(a) -> dict:
     out = {"envs": a.envs, "updates": a.updates, "runs": a.runs, "default": [], "control": [], "parent": [],
-           "parent_control": []}
+           "parent_control": [], "norm": []}
     _train_run(REPO, a)  # a first run nobody counts: the box's caches
     for k in range(a.runs):
         if a.parent_tree:
@@ -54,15 +56,20 @@ def train_probe(a) -> dict:
         if a.parent_tree and a.parent_control:
             out["parent_control"].append(_train_run(os.path.abspath(a.parent_tree), a, ("--target-kl", "inf")))
         out["default"].append(_train_run(REPO, a))
-        out["control"].append(_train_run(REPO, a, ("--target-kl", "inf")))
+        if a.norm_reward:
+            out["norm"].append(_train_run(REPO, a, ("--norm-reward",)))
+        else:
+            out["control"].append(_train_run(REPO, a, ("--target-kl", "inf")))
         print(json.dumps({"run": k, **{n: out[n][-1] for n in ARMS if out[n]}}), flush=True)
-    for key in ("whole_run", "steady_median", "train_s_median"):
+    for key in ("whole_run", "steady_median", "train_s_median", "rollout_s_median"):
         out[key] = {}
         for n in ARMS:
             v = [x[key] for x in out[n]]
             if v:
                 out[key].update({n + "_median": statistics.median(v), n + "_min": min(v), n + "_max": max(v)})
-        out[key]["control_over_default"] = out[key]["control_median"] / out[key]["default_median"]
+        for n in ("control", "norm"):
+            if out[n]:
+                out[key][n + "_over_default"] = out[key][n + "_median"] / out[key]["default_median"]
         if a.parent_tree:
             out[key]["default_inside_parent_spread"] = (out[key]["parent_min"] <= out[key]["default_median"]
                                                         <= out[key]["parent_max"])
@@ -116,6 +123,7 @@ def main():
     ap.add_argument("--updates", type=int, default=30)
     ap.add_argument("--parent-tree", default=None)
     ap.add_argument("--parent-control", action="store_true", help="also run the parent tree with --target-kl inf")
+    ap.add_argument("--norm-reward", action="store_true", help="train: this tree with --norm-reward in place of the control arm")
     ap.add_argument("--out", default=None, help="result file (default: profiles/ppo_control/<mode>_probe.json)")
     a = ap.parse_args()
     res = train_probe(a) if a.mode == "train" else stop_probe(a)

@@ -5,6 +5,7 @@
                               [--save AGENT.zip] [--checkpoint-every STEPS] [--resume AGENT.zip]
                               [--log-dir DIR [--no-tensorboard]]
                               [--lr-end LR] [--clip-range-end C] [--clip-range-vf C] [--target-kl KL]
+                              [--norm-reward [--clip-reward X]]
 
 One JSON line per update (timesteps, mean finished-episode return, losses, env-steps/s including
 the policy forward passes and the PPO update) into gpurun_out/ppo.jsonl and on stdout.
@@ -20,6 +21,8 @@ event file, ``env_train_config.txt`` and ``rl_config.txt`` there (drone2d_amd.tr
 ``tensorboard_log="logs"`` + ``TensorboardLogger``, main.py:192-208).
 ``--lr-end`` / ``--clip-range-end`` (linear schedules over the run's ``--updates``), ``--clip-range-vf`` and
 ``--target-kl`` (``inf``: log approx_kl only) select PPO's control path (PPOConfig; DESIGN.md "PPO control").
+``--norm-reward`` normalises the rewards the rollout records as SB3's ``VecNormalize(norm_obs=False, norm_reward=True)``
+does, clipped at ``--clip-reward`` (default 10; DESIGN.md "Reward normalisation"); the logs keep the raw returns.
 """
 from __future__ import annotations
 
@@ -60,6 +63,9 @@ def main():
     ap.add_argument("--clip-range-vf", type=float, default=None, help="SB3 clip_range_vf")
     ap.add_argument("--target-kl", type=float, default=None,
                     help="SB3 target_kl: stop an update when a minibatch's approx_kl exceeds 1.5 x this (inf: log only)")
+    ap.add_argument("--norm-reward", action="store_true",
+                    help="normalise the rollout's rewards by the running std of the discounted returns (VecNormalize)")
+    ap.add_argument("--clip-reward", type=float, default=10.0, metavar="X", help="with --norm-reward: clip at +-X")
     a = ap.parse_args()
 
     import torch
@@ -77,7 +83,8 @@ def main():
     venv = d2.Drone2dVecEnv(a.envs, seed=a.seed, **kw)
     cfg = PPOConfig.gpu_defaults(n_steps=a.n_steps, batch_size=a.batch, n_epochs=a.epochs,
                                  learning_rate_end=a.lr_end, clip_range_end=a.clip_range_end,
-                                 clip_range_vf=a.clip_range_vf, target_kl=a.target_kl)
+                                 clip_range_vf=a.clip_range_vf, target_kl=a.target_kl, norm_reward=a.norm_reward,
+                                 clip_reward=a.clip_reward)
     cfg.graph = not a.no_graph
     cfg.manual = not a.autograd
     # a resumed run takes its configuration, seed and env state from the file
@@ -87,7 +94,7 @@ def main():
         ck_dir = os.path.dirname(os.path.abspath(a.save)) if a.save else "ppo_agents"
         ckpt = Checkpoint(a.checkpoint_every, ck_dir)
     os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
-    tag = ("_eager" if a.no_graph else "") + ("_autograd" if a.autograd else "")
+    tag = ("_eager" if a.no_graph else "") + ("_autograd" if a.autograd else "") + ("_norm" if a.norm_reward else "")
     out = open(os.path.join(REPO, "gpurun_out", f"ppo{tag}.jsonl"), "w")
     logger = None
     if a.log_dir:
