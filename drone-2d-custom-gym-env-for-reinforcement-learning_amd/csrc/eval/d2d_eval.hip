@@ -1,6 +1,7 @@
 // libd2d_eval.so -- the fused evaluation step (include/d2d_eval.h): the first-episode recorder over env
 // step t-1's outputs and the SB3 MlpPolicy actor + policy noise + clip for step t, one launch; with a
-// policy bank (d2d_eval_step_bank) every env acts under the policy its map entry names.
+// policy bank (d2d_eval_step_bank) every env acts under the policy its map entry names; the sequenced
+// step (d2d_eval_step_seq) reads the call index from device memory, so a captured loop replays.
 #include <hip/hip_runtime.h>
 
 #include <climits>
@@ -31,8 +32,8 @@ static_assert(BK_LOG_STD + ACT == D2D_EVAL_BANK_STRIDE, "the bank's layout is th
 #endif
 
 // The record half for env i (one lane of wave 0 each); returns whether the env finished its first
-// episode at step t-1.
-__device__ __forceinline__ bool record_env(const d2d_eval_step_args& A, int i) {
+// episode at step t-1.  `flight_ok`: t - 1 is a row of flight (the host checked it for a by-value t).
+__device__ __forceinline__ bool record_env(const d2d_eval_step_args& A, int i, int t, bool flight_ok) {
     const bool done = (A.prev_term[i] | A.prev_trunc[i]) != 0;
     const bool fin = A.finished[i] != 0;
     const bool fresh = done && !fin;
@@ -41,9 +42,9 @@ __device__ __forceinline__ bool record_env(const d2d_eval_step_args& A, int i) {
         float* dst = A.rows + (size_t)i * A.info_dim;
         for (int k = 0; k < A.info_dim; ++k) dst[k] = src[k];
     }
-    if (A.flight != nullptr && !fin) {
+    if (A.flight != nullptr && flight_ok && !fin) {
         const float* src = (done ? A.prev_term_obs : A.obs) + (size_t)i * OBS + 6;
-        float* dst = A.flight + ((size_t)(A.t - 1) * A.n + i) * 2;
+        float* dst = A.flight + ((size_t)(t - 1) * A.n + i) * 2;
         dst[0] = src[0];
         dst[1] = src[1];
     }
@@ -70,8 +71,13 @@ __device__ __forceinline__ int wave_min(int v) {
 // policy is not the one already there, computes all 64 rows and keeps those whose policy it is.  A
 // kept row therefore went through exactly the chains above with its own policy's weights: the action
 // d2d_eval_step gives it under that policy alone.  An id outside [0, P) joins no pass.
-template <bool BANK>
-__global__ __launch_bounds__(BLOCK) void d2d_eval_step_kernel(d2d_eval_step_args A, d2d_eval_bank B) {
+//
+// SEQ (d2d_eval_step_seq): the call index is *t_dev, read here by every workgroup, and what the host
+// checks of a by-value t is decided here: the record half runs for t >= 1, flight is written for
+// 1 <= t <= flight_cap only.  Nothing in this launch writes *t_dev (d2d_eval_seq_bump does, afterwards).
+template <bool BANK, bool SEQ>
+__global__ __launch_bounds__(BLOCK) void d2d_eval_step_kernel(d2d_eval_step_args A, d2d_eval_bank B,
+                                                              const int32_t* t_dev) {
     __shared__ float w1s[HID * OBS];
     __shared__ float w2s[HID * HS];
     __shared__ float w3s[ACT][HID];
@@ -82,7 +88,9 @@ __global__ __launch_bounds__(BLOCK) void d2d_eval_step_kernel(d2d_eval_step_args
     const int tid = threadIdx.x, n = A.n;
     const int w = tid >> 6, lane = tid & 63, ci = lane & 31, h = lane >> 5;
     const int r0 = (w >> 1) * TILE, j0 = (w & 1) * TILE;  // this wave's env rows and units
-    const bool record = A.prev_term != nullptr;
+    const int t_call = SEQ ? *t_dev : A.t;
+    const bool record = A.prev_term != nullptr && (!SEQ || t_call >= 1);
+    const bool flight_ok = !SEQ || t_call <= A.flight_cap;
     auto stage = [&](const float* w1, const float* b1, const float* w2, const float* b2, const float* w3,
                      const float* b3) {
         for (int e = tid; e < HID * OBS; e += BLOCK) w1s[e] = w1[e];
@@ -173,7 +181,7 @@ __global__ __launch_bounds__(BLOCK) void d2d_eval_step_kernel(d2d_eval_step_args
                     z0 = A.noise[2 * (size_t)i];
                     z1 = A.noise[2 * (size_t)i + 1];
                 } else {
-                    policy_noise(A.seed, (uint32_t)(A.env_id_base + i), (uint32_t)A.t, D2D_EVAL_NOISE_TAG, z0, z1);
+                    policy_noise(A.seed, (uint32_t)(A.env_id_base + i), (uint32_t)t_call, D2D_EVAL_NOISE_TAG, z0, z1);
                 }
                 if (A.noise_out != nullptr) {
                     A.noise_out[2 * (size_t)i] = z0;
@@ -192,7 +200,7 @@ __global__ __launch_bounds__(BLOCK) void d2d_eval_step_kernel(d2d_eval_step_args
         if (BANK && A.act && sb + lane < n) pid = B.env_policy[sb + lane];
         if (record && w == 0) {  // wave 0, one env per lane
             const int i = sb + lane;
-            const bool fresh = i < n && record_env(A, i);
+            const bool fresh = i < n && record_env(A, i, t_call, flight_ok);
             const int cnt = __popcll(__ballot(fresh));
             if (lane == 0 && cnt) atomicSub(A.remaining, cnt);
         }
@@ -208,6 +216,10 @@ __global__ __launch_bounds__(BLOCK) void d2d_eval_step_kernel(d2d_eval_step_args
     }
 }
 
+// d2d_eval_step_seq's second launch: one thread moves the call index on once every workgroup of the step
+// has read it (stream order), as d2d_ppo_permute's trailing launch moves its shuffle counter.
+__global__ void d2d_eval_seq_bump(int32_t* t_dev) { t_dev[0] = t_dev[0] + 1; }
+
 }  // namespace
 
 extern "C" {
@@ -217,7 +229,8 @@ int32_t d2d_eval_abi_version(void) { return D2D_EVAL_ABI_VERSION; }
 int32_t d2d_eval_bank_version(void) { return D2D_EVAL_BANK_VERSION; }
 
 // Arguments that do not contradict each other; the actor comes from A (bank == nullptr) or from the bank.
-static bool args_ok(const d2d_eval_step_args& A, const d2d_eval_bank* bank) {
+// seq: the call index lives on the device, so what depends on it is the kernel's to decide.
+static bool args_ok(const d2d_eval_step_args& A, const d2d_eval_bank* bank, bool seq = false) {
     const bool record = A.prev_term != nullptr;
     bool ok = A.n > 0 && A.t >= 0 && (A.act != 0 || record);
     if (bank) {
@@ -235,7 +248,7 @@ static bool args_ok(const d2d_eval_step_args& A, const d2d_eval_bank* bank) {
     }
     if (record) {
         ok = ok && A.prev_trunc && A.prev_info && A.finished && A.rows && A.remaining && A.info_dim > 0;
-        if (A.flight) ok = ok && A.obs && A.prev_term_obs && A.t >= 1 && A.t <= A.flight_cap;
+        if (A.flight) ok = ok && A.obs && A.prev_term_obs && (seq ? A.flight_cap >= 0 : A.t >= 1 && A.t <= A.flight_cap);
     } else {
         // a partly given record half is a caller's mistake, not a request to skip it
         ok = ok && !A.prev_trunc && !A.prev_info;
@@ -250,15 +263,33 @@ static int grid_for(int n) {
 
 int32_t d2d_eval_step(const d2d_eval_step_args* args, void* stream) {
     if (args == nullptr || !args_ok(*args, nullptr)) return (int32_t)hipErrorInvalidValue;
-    hipLaunchKernelGGL(d2d_eval_step_kernel<false>, dim3(grid_for(args->n)), dim3(BLOCK), 0, (hipStream_t)stream,
-                       *args, d2d_eval_bank{});
+    hipLaunchKernelGGL((d2d_eval_step_kernel<false, false>), dim3(grid_for(args->n)), dim3(BLOCK), 0, (hipStream_t)stream,
+                       *args, d2d_eval_bank{}, (const int32_t*)nullptr);
     return (int32_t)hipGetLastError();
 }
 
 int32_t d2d_eval_step_bank(const d2d_eval_step_args* args, const d2d_eval_bank* bank, void* stream) {
     if (args == nullptr || bank == nullptr || !args_ok(*args, bank)) return (int32_t)hipErrorInvalidValue;
-    hipLaunchKernelGGL(d2d_eval_step_kernel<true>, dim3(grid_for(args->n)), dim3(BLOCK), 0, (hipStream_t)stream,
-                       *args, *bank);
+    hipLaunchKernelGGL((d2d_eval_step_kernel<true, false>), dim3(grid_for(args->n)), dim3(BLOCK), 0, (hipStream_t)stream,
+                       *args, *bank, (const int32_t*)nullptr);
+    return (int32_t)hipGetLastError();
+}
+
+int32_t d2d_eval_seq_version(void) { return D2D_EVAL_SEQ_VERSION; }
+
+int32_t d2d_eval_step_seq(const d2d_eval_step_args* args, const d2d_eval_bank* bank, int32_t* t_dev, void* stream) {
+    if (args == nullptr || t_dev == nullptr || args->t != 0 || !args_ok(*args, bank, true))
+        return (int32_t)hipErrorInvalidValue;
+    const dim3 grid(grid_for(args->n)), block(BLOCK);
+    if (bank)
+        hipLaunchKernelGGL((d2d_eval_step_kernel<true, true>), grid, block, 0, (hipStream_t)stream, *args, *bank,
+                           (const int32_t*)t_dev);
+    else
+        hipLaunchKernelGGL((d2d_eval_step_kernel<false, true>), grid, block, 0, (hipStream_t)stream, *args,
+                           d2d_eval_bank{}, (const int32_t*)t_dev);
+    const hipError_t e = hipGetLastError();
+    if (e != hipSuccess) return (int32_t)e;
+    hipLaunchKernelGGL(d2d_eval_seq_bump, dim3(1), dim3(1), 0, (hipStream_t)stream, t_dev);
     return (int32_t)hipGetLastError();
 }
 

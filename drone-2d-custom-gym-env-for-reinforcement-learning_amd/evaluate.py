@@ -7,6 +7,11 @@ side of every step -- the actor, its noise, the clip and the first-episode recor
 step t is a Philox draw keyed by (seed, g, t) and the actor's arithmetic is row-invariant, so a batch
 sharded over ranks or split into smaller batches flies, bit for bit, the episodes of the unsharded one.
 There is no fallback on a HIP batch: a missing library is an error.
+
+``graph=True`` (``EvalLoop``) flies the same loop as one captured segment of (``d2d_eval_step_seq``,
+``venv.step``) iterations replayed: the sequenced step reads its call index from device memory, so the
+index moves on from replay to replay.  The results are the eager loop's bit for bit; whether it is
+faster is measured in DESIGN.md "The replayed loop".
 """
 from __future__ import annotations
 
@@ -22,6 +27,7 @@ ABI_VERSION = 1
 NOISE_NONE, NOISE_GIVEN, NOISE_PHILOX = 0, 1, 2
 NOISE_TAG = 0x45560000
 BANK_VERSION = 1
+SEQ_VERSION = 1
 BANK_STRIDE = 6084  # floats per policy in a bank: W1, b1, W2, b2, W3, b3, log_std (include/d2d_eval.h)
 _BANK_SHAPES = ((64, 27), (64,), (64, 64), (64,), (2, 64), (2,), (2,))
 LIB_PATH = os.path.join(os.path.dirname(os.path.abspath(__file__)), "_lib", "libd2d_eval.so")
@@ -52,17 +58,20 @@ SIGNATURES = {
     "d2d_eval_step": (C.c_int32, [C.POINTER(D2DEvalStepArgs), _VP]),
     "d2d_eval_bank_version": (C.c_int32, []),
     "d2d_eval_step_bank": (C.c_int32, [C.POINTER(D2DEvalStepArgs), C.POINTER(D2DEvalBank), _VP]),
+    "d2d_eval_seq_version": (C.c_int32, []),
+    "d2d_eval_step_seq": (C.c_int32, [C.POINTER(D2DEvalStepArgs), C.POINTER(D2DEvalBank), _VP, _VP]),
 }
 
 _lib = None
 
 
 def bind(path: str) -> C.CDLL:
-    """The library at ``path`` with its signatures set and its ABI and bank versions checked."""
+    """The library at ``path`` with its signatures set and its ABI, bank and sequenced-step versions checked."""
     from . import _native
 
     lib = _native.bind(path, SIGNATURES, "d2d_eval_abi_version", ABI_VERSION, EvalError)
     _native.check_version(lib, path, "d2d_eval_bank_version", BANK_VERSION, EvalError, None)
+    _native.check_version(lib, path, "d2d_eval_seq_version", SEQ_VERSION, EvalError, None)
     return lib
 
 
@@ -88,6 +97,13 @@ def _step_bank(lib, args: D2DEvalStepArgs, bank: D2DEvalBank, stream: int) -> No
     rc = lib.d2d_eval_step_bank(C.byref(args), C.byref(bank), stream)
     if rc:
         raise EvalError(f"d2d_eval_step_bank: hipError {rc}" + (" (contradictory arguments)" if rc == 1 else ""))
+
+
+def _step_seq(lib, args: D2DEvalStepArgs, bank: D2DEvalBank | None, t_dev: int, stream: int) -> None:
+    """``d2d_eval_step_seq``: the call index is the device int32 at ``t_dev``; two launches."""
+    rc = lib.d2d_eval_step_seq(C.byref(args), C.byref(bank) if bank is not None else None, t_dev, stream)
+    if rc:
+        raise EvalError(f"d2d_eval_step_seq: hipError {rc}" + (" (contradictory arguments)" if rc == 1 else ""))
 
 
 def _actor_critic(policy):
@@ -237,7 +253,7 @@ def _records(venv, fin, rows_np, xy_np, nobs) -> dict:
 @torch.no_grad()
 def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0, max_steps: int | None = None,
                     n_obstacles: int | None = None, flight_paths: bool = False, check_every: int = 16,
-                    noise: str = "philox", keep_actions: bool = False) -> dict:
+                    noise: str = "philox", keep_actions: bool = False, graph: bool = False) -> dict:
     """Step ``venv`` under ``policy`` (an ``ActorCritic``, a ``harness.MlpActor`` or a ``ppo.PPO``)
     until every env has finished its first episode; the result dict of
     ``harness.run_first_episodes`` (+ ``actions`` [steps, n, 2] with ``keep_actions``: this rank's).
@@ -253,6 +269,9 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
     as ``run_first_episodes`` draws it.  With ``torch.distributed`` initialised rank 0 gathers every
     rank's records in global env order, as ``run_first_episodes`` does.
 
+    ``graph``: replay the loop as a captured HIP graph (a throw-away ``EvalLoop``): the same result
+    dict, bit for bit.  It needs a HIP batch, ``noise="philox"``, ``keep_actions=False`` and one rank.
+
     A batch that is not a HIP ``Drone2dVecEnv`` (the CPU oracle backend of the tests) goes through
     ``harness.run_first_episodes``."""
     from . import harness
@@ -260,6 +279,8 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
 
     if noise not in ("philox", "torch"):
         raise ValueError("noise must be 'philox' or 'torch'")
+    if graph:
+        _check_graph(venv, noise, keep_actions)
     if not isinstance(venv, Drone2dVecEnv):
         if keep_actions:
             raise ValueError("keep_actions needs a HIP batch")
@@ -267,15 +288,32 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
                                           max_steps=max_steps, n_obstacles=n_obstacles, flight_paths=flight_paths,
                                           check_every=check_every)
     fin, rows_np, xy_np, nobs, actions, _ = _fly(venv, actor_tensors(policy, venv.device), None, deterministic, seed,
-                                                 max_steps, n_obstacles, flight_paths, check_every, noise, keep_actions)
+                                                 max_steps, n_obstacles, flight_paths, check_every, noise, keep_actions,
+                                                 graph=graph)
     out = _records(venv, fin, rows_np, xy_np, nobs)
     if keep_actions:
         out["actions"] = actions
     return out
 
 
+def _check_graph(venv, noise, keep_actions) -> None:
+    """What ``graph=True`` cannot do, as a ``ValueError``."""
+    from . import harness
+    from .env import Drone2dVecEnv
+
+    if not isinstance(venv, Drone2dVecEnv):
+        raise ValueError("graph=True needs a HIP Drone2dVecEnv: the replayed loop is the device's")
+    if noise != "philox":
+        raise ValueError("graph=True with noise='torch': a host draw per step cannot be captured; use noise='philox'")
+    if keep_actions:
+        raise ValueError("graph=True with keep_actions=True: the replayed loop keeps no per-step copies")
+    if harness._dist_world()[2] > 1:
+        raise ValueError("graph=True with more than one rank: the gather of the records stays eager and the replayed "
+                         "loop is built for one rank")
+
+
 def _fly(venv, ws, bank, deterministic, seed, max_steps, n_obstacles, flight_paths, check_every, noise, keep_actions,
-         extra=()):
+         extra=(), graph=False):
     """The closed loop of ``evaluate_policy`` on a HIP batch under one actor (``ws``, its seven tensors)
     or a policy bank (``bank``: a ``D2DEvalBank`` whose tensors the caller keeps alive): the recorder's
     arrays over the whole batch in global env order (gathered over the ranks, and with them the
@@ -284,6 +322,11 @@ def _fly(venv, ws, bank, deterministic, seed, max_steps, n_obstacles, flight_pat
 
     if not venv.with_info:
         raise ValueError("evaluate_policy needs the env's info rows (with_info=True)")
+    if graph:
+        _check_graph(venv, noise, keep_actions)
+        loop = EvalLoop(venv, None, deterministic=deterministic, flight_paths=flight_paths, check_every=check_every,
+                        graph=True, max_steps=max_steps, n_obstacles=n_obstacles, _actor=(ws, bank))
+        return loop.run(seed, extra=extra)
     lib = load()
     dev = venv.device
     dist, rank, world = harness._dist_world()
@@ -357,6 +400,172 @@ def _fly(venv, ws, bank, deterministic, seed, max_steps, n_obstacles, flight_pat
         # the call that found every env finished had already written the next step's actions: drop them
         actions = (torch.stack(actions[:steps]) if steps else torch.empty(0, n, 2, device=dev)).cpu().numpy()
     return fin, rows_np, xy_np, nobs, actions, extra
+
+
+class EvalLoop:
+    """The closed loop of ``evaluate_policy`` / ``evaluate_policies`` kept for many evaluations of one
+    batch: it owns the recorder's buffers, the device call index ``t_dev`` of ``d2d_eval_step_seq`` and,
+    with ``graph``, one captured segment of ``K`` iterations of (``d2d_eval_step_seq``, ``venv.step``),
+    ``K`` = ``check_every`` rounded up to even (the env's outputs are double-buffered: an even segment
+    ends on the buffer parity it began on, so it can be replayed back to back).
+
+    ``policy_or_bank``: one policy (``env_policy`` None) or a ``PolicyBank`` / list of policies with
+    the env -> policy map.  ``run(seed)`` rewinds -- the env's episode counters put back to what the
+    first run found (``set_state``: they key the spawn draws), ``venv.reset(seed)``, buffers cleared,
+    ``t_dev`` zeroed -- flies, and returns ``_fly``'s arrays, bit for bit those of the eager by-value
+    loop on a batch in the first run's state:
+
+      step 0 eagerly (no record half); on the first run one segment eagerly (library warm-up), then the
+      capture; replays, each followed by a read-back of ``remaining``, until it is 0 or fewer than K
+      steps are left before the cap; the tail and the record-only call eagerly.
+
+    The segment holds the actor's tensors by address and ``actor_tensors`` makes no copy of float32
+    device parameters, so a replay reads the live weights; ``run`` recaptures when one of the seven
+    addresses (the bank's one), the seed (the env step takes it by value) or the env's ``generation``
+    is not what the segment was captured with.  ``graph=False``: every run is ``_fly``'s eager loop."""
+
+    def __init__(self, venv, policy_or_bank, env_policy=None, *, deterministic: bool = False,
+                 flight_paths: bool = False, check_every: int = 16, graph: bool = True, max_steps: int | None = None,
+                 n_obstacles: int | None = None, _actor=None):
+        from .env import Drone2dVecEnv
+
+        if graph:
+            _check_graph(venv, "philox", False)
+        elif not isinstance(venv, Drone2dVecEnv):
+            raise ValueError("EvalLoop needs a HIP Drone2dVecEnv")
+        if not venv.with_info:
+            raise ValueError("evaluate_policy needs the env's info rows (with_info=True)")
+        if int(check_every) < 1:
+            raise ValueError("check_every must be at least 1")
+        self.venv, self.graph = venv, bool(graph)
+        self.deterministic, self.flight_paths, self.check_every = bool(deterministic), bool(flight_paths), int(check_every)
+        self.max_steps, self.n_obstacles = max_steps, n_obstacles
+        self.policy = self.bank = self._ep = None
+        self._fixed = _actor  # _fly's (ws, c_bank): tensors the caller keeps alive
+        if _actor is None:
+            if env_policy is None:
+                self.policy = policy_or_bank
+            else:
+                self.bank = _as_bank(policy_or_bank).to(venv.device)
+                self._ep = torch.from_numpy(check_env_policy(env_policy, int(venv.num_envs),
+                                                             self.bank.n_policies)).to(venv.device)
+        self.K = self.check_every + (self.check_every & 1)
+        self.captures = 0       # segments captured so far (1 after any number of runs of unmoved weights)
+        self._g = None
+        self._key = None        # what the segment was captured with
+        self._bufs = None
+        self._k0 = None
+        self._snap = None       # the env's state before the first run's reset
+
+    def _actor(self):
+        """(ws, c_bank, key): the seven tensors or the bank record, and the addresses a capture bakes in."""
+        if self._fixed is not None:
+            ws, cb = self._fixed
+        elif self.bank is not None:
+            ws, cb = None, self.bank.c_bank(self._ep)
+        else:
+            ws, cb = actor_tensors(self.policy, self.venv.device), None
+        key = tuple(t.data_ptr() for t in ws) if ws is not None else (cb.params, cb.env_policy, cb.n_policies)
+        return ws, cb, key
+
+    def _alloc(self, cap):
+        n, dev = int(self.venv.num_envs), self.venv.device
+        self._bufs = dict(
+            finished=torch.zeros(n, dtype=torch.uint8, device=dev),
+            rows=torch.zeros(n, abi.INFO_DIM, dtype=torch.float32, device=dev),
+            remaining=torch.full((1,), n, dtype=torch.int32, device=dev),
+            act_env=torch.empty(n, abi.ACT_DIM, dtype=torch.float32, device=dev),
+            t_dev=torch.zeros(1, dtype=torch.int32, device=dev),
+            pos=torch.full((cap, n, 2), float("nan"), dtype=torch.float32, device=dev) if self.flight_paths else None)
+
+    @torch.no_grad()
+    def run(self, seed: int = 0, extra=()):
+        venv = self.venv
+        ws, cb, key = self._actor()
+        # the env's episode counters key its spawn draws and a reset moves them on: put them back to
+        # where the first run found them, so that every run flies the first run's episodes
+        if self._snap is None:
+            self._snap = venv.get_state()
+        else:
+            venv.set_state(*self._snap)
+        if not self.graph:
+            return _fly(venv, ws, cb, self.deterministic, seed, self.max_steps, self.n_obstacles, self.flight_paths,
+                        self.check_every, "philox", False, extra)
+        lib = load()
+        dev = venv.device
+        n = int(venv.num_envs)
+        cap = int(self.max_steps) if self.max_steps is not None else int(venv.kwargs["n_steps"]) + 1
+        nobs = self.n_obstacles if self.n_obstacles is not None else (
+            len(venv.scenarios[0].circles) if venv.scenarios else 0)
+        K = self.K
+        with torch.cuda.device(dev):
+            if self._bufs is None:
+                self._alloc(cap)
+                self._k0 = venv._k  # the output-buffer parity every run starts on (the segment's addresses)
+            B = self._bufs
+            key = (key, int(seed), venv.generation)
+            if key != self._key:
+                self._g = None
+            self._ws = ws  # (alive while the segment points at them)
+            venv._k = self._k0
+            obs = venv.reset(seed=seed)
+            B["finished"].zero_()
+            B["rows"].zero_()
+            B["remaining"].fill_(n)
+            B["t_dev"].zero_()
+            if B["pos"] is not None:
+                B["pos"].fill_(float("nan"))
+            a = D2DEvalStepArgs(n=n, info_dim=abi.INFO_DIM, flight_cap=cap, env_id_base=int(venv.cfg.env_id_base),
+                                seed=int(seed) & (2 ** 64 - 1), act_env=B["act_env"].data_ptr(), act=1,
+                                noise_mode=NOISE_NONE if self.deterministic else NOISE_PHILOX, obs=obs.data_ptr())
+            if ws is not None:
+                _weights_into(a, ws)
+            t_dev = B["t_dev"].data_ptr()
+
+            def env_step():
+                # the env's outputs are double-buffered: this step's set stays valid through the next call
+                o, _, term, trunc, info = venv.step(B["act_env"])
+                a.obs = o.data_ptr()
+                a.prev_term, a.prev_trunc, a.prev_info = term.data_ptr(), trunc.data_ptr(), info.data_ptr()
+                a.prev_term_obs = venv.terminal_obs.data_ptr()
+                a.finished, a.rows, a.remaining = B["finished"].data_ptr(), B["rows"].data_ptr(), B["remaining"].data_ptr()
+                a.flight = B["pos"].data_ptr() if B["pos"] is not None else None
+
+            def segment():
+                for _ in range(K):
+                    _step_seq(lib, a, cb, t_dev, torch.cuda.current_stream(dev).cuda_stream)
+                    env_step()
+
+            # step 0: no record half (the prev_* pointers are still NULL)
+            _step_seq(lib, a, cb, t_dev, torch.cuda.current_stream(dev).cuda_stream)
+            env_step()
+            done = 1  # env steps taken = the next call's index
+            left = n
+            if self._g is None and done + K <= cap:
+                segment()  # eagerly first: the library's kernels loaded before the capture
+                done += K
+                torch.cuda.synchronize(dev)
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    segment()  # (recorded, not run; K is even, so `a` is back at this parity's pointers)
+                self._g, self._key = g, key
+                self.captures += 1
+                left = int(B["remaining"].item())
+            while left and done + K <= cap:
+                self._g.replay()
+                done += K
+                left = int(B["remaining"].item())
+            if left:
+                while done < cap:  # the tail: fewer than K steps before the cap
+                    _step_seq(lib, a, cb, t_dev, torch.cuda.current_stream(dev).cuda_stream)
+                    env_step()
+                    done += 1
+            a.act = 0  # the record-only call over the last env step's outputs
+            _step_seq(lib, a, cb, t_dev, torch.cuda.current_stream(dev).cuda_stream)
+            fin = B["finished"].cpu().numpy().astype(bool)
+            rows_np = B["rows"].cpu().numpy()
+            xy_np = B["pos"].cpu().numpy() if B["pos"] is not None else None
+        return fin, rows_np, xy_np, nobs, [], tuple(np.asarray(e) for e in extra)
 
 
 # ---------------------------------------------------------------- the policy bank: many agents in one batch
@@ -487,7 +696,7 @@ class BankActor(torch.nn.Module):
 @torch.no_grad()
 def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool = False, seed: int = 0,
                       max_steps: int | None = None, n_obstacles: int | None = None, flight_paths: bool = False,
-                      check_every: int = 16, noise: str = "philox", keep_actions: bool = False):
+                      check_every: int = 16, noise: str = "philox", keep_actions: bool = False, graph: bool = False):
     """``evaluate_policy`` for a batch whose envs belong to different agents: env i flies under policy
     ``env_policy[i]`` of ``bank`` (a ``PolicyBank`` or a list of policies), one ``d2d_eval_step_bank``
     per env step.  Returns one result dict per policy (a list), each what ``evaluate_policy`` returns,
@@ -499,12 +708,15 @@ def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool
     same batch: the actor is row-invariant across the bank, and noise and spawns are keyed by global
     env id.  Under ``torch.distributed`` every rank passes its shard's slice of the map (and of
     ``split``); the records are gathered in global env order and split afterwards.  A batch that is not
-    a HIP ``Drone2dVecEnv`` goes through ``harness.run_first_episodes`` under a ``BankActor``."""
+    a HIP ``Drone2dVecEnv`` goes through ``harness.run_first_episodes`` under a ``BankActor``.
+    ``graph``: as in ``evaluate_policy``."""
     from . import harness
     from .env import Drone2dVecEnv
 
     if noise not in ("philox", "torch"):
         raise ValueError("noise must be 'philox' or 'torch'")
+    if graph:
+        _check_graph(venv, noise, keep_actions)
     bank = _as_bank(bank)
     n = int(venv.num_envs)
     ep = check_env_policy(env_policy, n, bank.n_policies)
@@ -527,7 +739,7 @@ def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool
         ep_dev = torch.from_numpy(ep).to(venv.device)
         fin, rows_np, xy_np, nobs, actions, extra = _fly(venv, None, bank.c_bank(ep_dev), deterministic, seed, max_steps,
                                                          n_obstacles, flight_paths, check_every, noise, keep_actions,
-                                                         extra)
+                                                         extra, graph=graph)
     g_ep, g_labels = extra[0], (extra[1] if labels is not None else None)
 
     def subset(mask, local_mask):
@@ -555,12 +767,13 @@ def sweep_layout(n_policies: int, n_scenarios: int, runs: int) -> tuple:
 
 
 def sweep(bank, scenarios, runs: int, *, seed: int = 0, deterministic: bool = False, flight_paths: bool = False,
-          env_kwargs: dict | None = None) -> dict:
+          env_kwargs: dict | None = None, graph: bool = False) -> dict:
     """Every agent of ``bank`` on every scenario, ``runs`` first episodes each, as one batch of
     P S R envs (``sweep_layout``) in one closed loop: {agent name: {scenario name: result dict}}.
     ``scenarios``: names of static scenarios or ``Scenario`` objects (a curriculum stage is refused:
     pass a fresh-curriculum batch to ``evaluate_policies``); ``env_kwargs``: default ``ENV_TEST_CONFIG``.
-    Every (agent, scenario, run) is an env of its own global id, so its spawn and noise draws are its own."""
+    Every (agent, scenario, run) is an env of its own global id, so its spawn and noise draws are its own.
+    ``graph``: as in ``evaluate_policy``."""
     from .config import CURRICULUM_STAGES, ENV_TEST_CONFIG
     from .env import Drone2dVecEnv, is_curriculum
 
@@ -578,7 +791,7 @@ def sweep(bank, scenarios, runs: int, *, seed: int = 0, deterministic: bool = Fa
     venv = Drone2dVecEnv(len(ep), device=bank.device, seed=seed, with_info=True, env_scenario=es, **kw)
     try:
         res = evaluate_policies(venv, bank, ep, split=es, deterministic=deterministic, seed=seed,
-                                flight_paths=flight_paths)
+                                flight_paths=flight_paths, graph=graph)
     finally:
         venv.close()
     return {bank.names[p]: {names[s]: res[(p, s)] for s in range(len(names))} for p in range(bank.n_policies)}
@@ -586,4 +799,4 @@ def sweep(bank, scenarios, runs: int, *, seed: int = 0, deterministic: bool = Fa
 
 __all__ = ["evaluate_policy", "act", "actor_tensors", "as_mlp_actor", "philox_noise_host", "load", "bind", "EvalError",
            "D2DEvalStepArgs", "D2DEvalBank", "PolicyBank", "BankActor", "act_bank", "evaluate_policies", "sweep_layout",
-           "sweep", "check_env_policy"]
+           "sweep", "check_env_policy", "EvalLoop"]

@@ -23,6 +23,10 @@ this module restates the parts of SB3 2.1 that a training run executes, in the s
   rewards divided by the running standard deviation of the discounted returns (normalize.py,
   libd2d_norm.so; DESIGN.md "Reward normalisation"); episode statistics and logs stay raw.
 
+* ``Evaluation`` (SB3 ``EvalCallback``): ``learn(evaluation=...)`` flies the current policy on the test
+  scenarios every ``eval_freq`` steps in an env batch of its own, logs ``eval/*`` and keeps
+  ``evaluations.npz`` and ``best_model.zip`` (train_eval.py; DESIGN.md "The replayed loop").
+
 At 65 536 envs a 2 048-step rollout would hold 134 M transitions, so GPU-scale runs shorten
 n_steps and enlarge batch_size (``PPOConfig.gpu_defaults``); the update rule is unchanged.  With
 ``torch.distributed`` initialised (one process per GPU, each with its env shard,
@@ -44,6 +48,7 @@ import torch.distributed as dist
 
 from .agent_io import (AGENT_FORMAT_VERSION, AGENT_MEMBERS, _to_arrays, _to_tensors,  # noqa: F401  (re-exports)
                        read_agent, write_agent)
+from .config import TEST_SCENARIOS
 from .policy import _HALF_LOG_2PI, ActorCritic  # noqa: F401
 from .ppo_native import PPO_CTL_VERSION, D2DPPOCtl, D2DPPORollout, _ok, ppo_native  # noqa: F401
 from .ppo_step import STAT_KEYS, AutogradStep, ControlBlock, ManualStep  # noqa: F401
@@ -117,6 +122,46 @@ class Checkpoint:
     save_freq: int
     save_path: str
     name_prefix: str = "rl_model"
+
+
+@dataclass
+class Evaluation:
+    """``PPO.learn(evaluation=...)``: SB3's ``EvalCallback``.  After the update whose ``num_timesteps``
+    crosses a multiple of ``eval_freq`` the current policy flies ``runs`` first episodes on each of
+    ``scenarios`` -- one batch of S x ``runs`` envs, scenario-major (``evaluate.sweep_layout(1, S, runs)``), a
+    second env batch of its own -- and the update's record gains ``eval/mean_reward``,
+    ``eval/mean_ep_length`` (SB3's two), ``eval/success_rate``, ``eval/collision_rate``,
+    ``eval/average_ape`` (``harness.summary``'s numbers), ``eval/seconds``, ``eval/best`` and per scenario
+    ``eval/<scenario>/success_rate`` and ``eval/<scenario>/mean_reward``.
+
+    ``<log_path>/evaluations.npz`` holds SB3's ``timesteps`` [E], ``results`` [E, S runs] (episode returns
+    in env order) and ``ep_lengths`` [E, S runs], and ``successes``, ``collisions`` (same shape),
+    ``scenarios`` (the S names), ``metric`` [E] and ``metric_name``; it is rewritten after every
+    evaluation.  A file found when ``learn`` starts is continued when its scenarios, runs and metric
+    are this protocol's (the best metric so far is restored from it, so a resumed run does not
+    overwrite a better ``best_model.zip``); otherwise ``learn`` raises.  ``<best_model_save_path>/
+    best_model.zip`` is ``PPO.save`` whenever ``metric`` is strictly greater than the best so far (SB3's
+    ``>``: the first of equal scores stays; a NaN never wins).
+
+    Deviations from SB3, on purpose: (1) SB3 evaluates in mid-rollout, whenever its step counter hits
+    ``eval_freq``; here the evaluation runs after the update, as ``checkpoint`` does, so the policy
+    evaluated is the one a checkpoint of that step holds.  (2) SB3 lets its eval env run on from one
+    evaluation to the next; here every evaluation resets the eval batch to the same ``seed``, so
+    successive evaluations face the same spawn draws and differ by the policy alone.
+
+    ``graph``: fly the eval loop as a replayed HIP graph (``evaluate.EvalLoop``); None: what measured
+    faster (``train_eval.GRAPH_PAYS``).  One rank only: ``learn`` raises with more."""
+    eval_freq: int                               # num_timesteps (this rank's), Checkpoint.save_freq's unit
+    scenarios: tuple = TEST_SCENARIOS            # static scenario names or Scenario objects
+    runs: int = 16                               # episodes per scenario; n_eval_episodes = S * runs
+    deterministic: bool = True                   # SB3's default
+    seed: int = 0
+    metric: str = "mean_reward"                  # or "success_rate"; larger is better
+    log_path: str | None = None                  # <log_path>/evaluations.npz
+    best_model_save_path: str | None = None      # <path>/best_model.zip
+    env_kwargs: dict | None = None               # default ENV_TEST_CONFIG
+    graph: bool | None = None
+    venv_factory: object = None                  # (num_envs, env_scenario, seed, **kw) -> batch; None: Drone2dVecEnv
 
 
 def compute_gae(rewards, values, episode_starts, last_values, last_dones, gamma, gae_lambda):
@@ -198,6 +243,7 @@ class PPO:
         self._fused = None       # decided at the first rollout (_alloc_rollout)
         self._predict_t = 0      # predict()'s call counter: the Philox step index of its noise
         self._predict_gen = None
+        self._ev_run = None      # learn(evaluation=...)'s EvaluationRun: the eval batch and its loop
         self.monitor = None      # an EpisodeMonitor (set_monitor / learn(monitor=...)); None: off
         self.normalizer = None   # a RewardNormalizer (cfg.norm_reward); None: the rollout records raw rewards
         if self.cfg.norm_reward:
@@ -539,7 +585,7 @@ class PPO:
         return ctl.read() if ctl is not None else {k: float(v) / max(n_upd, 1) for k, v in self._acc.items()}
 
     def learn(self, total_timesteps: int, log=None, checkpoint: Checkpoint | None = None, monitor=None,
-              logger=None, schedule_timesteps: int | None = None) -> list[dict]:
+              logger=None, schedule_timesteps: int | None = None, evaluation: Evaluation | None = None) -> list[dict]:
         """Alternate rollouts and updates until ``total_timesteps`` env steps (this rank);
         ``checkpoint``: save the agent whenever ``num_timesteps`` crosses a multiple of its
         ``save_freq`` (after the update, so a resumed run continues with the next rollout).
@@ -549,10 +595,38 @@ class PPO:
         update, ``progress_remaining = 1 - num_timesteps / total_timesteps`` (SB3's
         ``OnPolicyAlgorithm.learn``; not below 0 when the last rollout overshoots), which the schedules
         ``learning_rate_end`` / ``clip_range_end`` read; ``schedule_timesteps``: the schedule's horizon
-        when it is not this call's ``total_timesteps`` (a run driven by several ``learn`` calls)."""
+        when it is not this call's ``total_timesteps`` (a run driven by several ``learn`` calls).
+        ``evaluation``: an ``Evaluation`` -- the policy is flown on test scenarios after the update whose
+        ``num_timesteps`` crosses a multiple of its ``eval_freq`` (before that update's checkpoint), and
+        that update's record gains ``eval/*``; the eval batch is built at the first evaluation and kept (also
+        for a later ``learn`` call with the same object; ``close_evaluation`` drops it).  None: nothing
+        is launched or written for it."""
         horizon = float(schedule_timesteps if schedule_timesteps is not None else total_timesteps)
         if monitor is not None:
             self.set_monitor(monitor)
+        ev_run = None
+        if evaluation is not None:
+            if self.world > 1:
+                raise ValueError("evaluation=... with more than one rank: every rank would fly the whole eval batch "
+                                 "and keep files of its own, and an evaluation sharded over the ranks is not built")
+            from .train_eval import EvaluationRun
+
+            # a run driven by several learn calls with one Evaluation object keeps its eval batch, its
+            # captured loop and its best metric from call to call
+            if self._ev_run is None or self._ev_run.ev is not evaluation:
+                self.close_evaluation()
+                self._ev_run = EvaluationRun(evaluation, self)
+            ev_run = self._ev_run
+        return self._learn(total_timesteps, horizon, log, checkpoint, logger, ev_run)
+
+    def close_evaluation(self):
+        """Drop the eval batch a ``learn(evaluation=...)`` built (it is otherwise kept for the next
+        ``learn`` call with the same ``Evaluation`` object, and closed with this object)."""
+        if self._ev_run is not None:
+            self._ev_run.close()
+        self._ev_run = None
+
+    def _learn(self, total_timesteps, horizon, log, checkpoint, logger, ev_run) -> list[dict]:
         hist = []
         while self.num_timesteps < total_timesteps:
             before = self.num_timesteps
@@ -568,6 +642,8 @@ class PPO:
             t2 = time.perf_counter()
             rec = dict(ro, **tr, timesteps=self.num_timesteps, rollout_s=t1 - t0, train_s=t2 - t1,
                        env_steps_per_s=self.cfg.n_steps * self.n_envs / (t2 - t0))
+            if ev_run is not None and ev_run.due(before, self.num_timesteps):
+                rec.update(ev_run(self))
             hist.append(rec)
             if log:
                 log(rec)
@@ -673,4 +749,4 @@ class PPO:
         return algo
 
 
-__all__ = ["PPOConfig", "Checkpoint", "ActorCritic", "ManualStep", "PPO", "compute_gae"]
+__all__ = ["PPOConfig", "Checkpoint", "Evaluation", "ActorCritic", "ManualStep", "PPO", "compute_gae"]

@@ -94,14 +94,14 @@ _TRAIN_KEYS = ("policy_loss", "value_loss", "entropy", "clip_fraction", "approx_
 def record_scalars(rec: dict, total_episodes: float | None = None) -> dict:
     """A ``PPO.learn`` record under the log's names: ``monitor/<key>`` -> ``<key>`` (``monitor/episodes``
     and ``monitor/skipped`` -> ``rollout/episodes`` / ``rollout/skipped``), the update's statistics ->
-    ``train/*``, ``norm/*`` as they are, ``time/fps``, ``time/total_timesteps`` and, with ``total_episodes``, the reference's
+    ``train/*``, ``norm/*`` and ``eval/*`` as they are, ``time/fps``, ``time/total_timesteps`` and, with ``total_episodes``, the reference's
     cumulative ``time/episodes``."""
     out = {}
     for k, v in rec.items():
         if k.startswith("monitor/"):
             k = k[len("monitor/"):]
             out[k if "/" in k else "rollout/" + k] = v
-        elif k.startswith(("train/", "norm/")):
+        elif k.startswith(("train/", "norm/", "eval/")):
             out[k] = v
         elif k in _TRAIN_KEYS:
             out["train/" + k] = v

@@ -108,6 +108,31 @@ int32_t d2d_eval_bank_version(void);
  * with act != 0 a NULL params or env_policy (act == 0 reads neither), or what d2d_eval_step rejects. */
 int32_t d2d_eval_step_bank(const d2d_eval_step_args* args, const d2d_eval_bank* bank, void* stream);
 
+/* The sequenced step: d2d_eval_step (bank == NULL) or d2d_eval_step_bank with one difference: the call
+ * index is *t_dev (a device int32), read when the kernel runs, so a captured segment of (d2d_eval_step_seq,
+ * d2d_step) iterations replays with the index moving on.  Additive: the functions above, the argument
+ * struct, D2D_EVAL_ABI_VERSION and D2D_EVAL_BANK_VERSION are unchanged, and so are the bits they produce.
+ *
+ * The index.  args->t must be 0; t = *t_dev feeds exactly what args->t feeds above: the Philox counter
+ *   word of noise mode 2 and the flight[t-1] row.
+ * Checks.  What the host checks of a by-value t the kernel decides: the record half runs when the prev_*
+ *   pointers are non-NULL and t >= 1 (t = 0 with them given is a skipped record half, not an error);
+ *   flight is written only for 1 <= t <= flight_cap, beyond that nothing of flight is touched and the
+ *   rest of the step is done.  Every check that does not involve t stays on the host:
+ *   hipErrorInvalidValue (nothing launched) for t_dev NULL, args->t != 0, flight_cap < 0 with flight
+ *   given, or what d2d_eval_step / d2d_eval_step_bank reject.
+ * The increment.  The call issues TWO launches: the step, every workgroup of which reads *t_dev and none
+ *   of which writes it, then a one-thread launch that stores t + 1 (a plain store), ordered after the
+ *   whole step by the stream, so no late-starting workgroup can see the moved index.  After the call
+ *   *t_dev is t + 1; the caller rewinds it with an ordinary stream-ordered write.
+ * Invariance.  Row invariance and bank invariance carry over word for word: for the same t every output
+ *   (act_env, noise_out, rows, finished, flight, remaining) is the by-value call's, bit for bit.
+ * Capture.  Stream-ordered, no synchronisation, no allocation: the call captures into a HIP graph. */
+#define D2D_EVAL_SEQ_VERSION 1
+int32_t d2d_eval_seq_version(void);
+int32_t d2d_eval_step_seq(const d2d_eval_step_args* args, const d2d_eval_bank* bank /* NULL: one actor */,
+                          int32_t* t_dev, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

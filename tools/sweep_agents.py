@@ -55,6 +55,7 @@ def main():
     ap.add_argument("--deterministic", action="store_true")
     ap.add_argument("--flight-paths", action="store_true")
     ap.add_argument("--out", default=None)
+    ap.add_argument("--graph", action="store_true", help="replay the sweep's loop as a captured HIP graph (same results)")
     a = ap.parse_args()
 
     import torch
@@ -72,7 +73,8 @@ def main():
     out_root = a.out or "Tests"
     t0 = time.perf_counter()
     bank = evaluate.PolicyBank(paths, names=names, device=torch.device("cuda", 0))
-    res = evaluate.sweep(bank, scns, a.envs, seed=a.seed, deterministic=a.deterministic, flight_paths=a.flight_paths)
+    res = evaluate.sweep(bank, scns, a.envs, seed=a.seed, deterministic=a.deterministic, flight_paths=a.flight_paths,
+                         graph=a.graph)
     seconds = round(time.perf_counter() - t0, 3)
     for name, path in zip(names, paths):
         for scn in scns:

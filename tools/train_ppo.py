@@ -6,6 +6,7 @@
                               [--log-dir DIR [--no-tensorboard]]
                               [--lr-end LR] [--clip-range-end C] [--clip-range-vf C] [--target-kl KL]
                               [--norm-reward [--clip-reward X]]
+                              [--eval-freq STEPS [--eval-runs R] [--eval-scenarios a,b,...] [--eval-metric M]]
 
 One JSON line per update (timesteps, mean finished-episode return, losses, env-steps/s including
 the policy forward passes and the PPO update) into gpurun_out/ppo.jsonl and on stdout.
@@ -23,6 +24,10 @@ event file, ``env_train_config.txt`` and ``rl_config.txt`` there (drone2d_amd.tr
 ``--target-kl`` (``inf``: log approx_kl only) select PPO's control path (PPOConfig; DESIGN.md "PPO control").
 ``--norm-reward`` normalises the rewards the rollout records as SB3's ``VecNormalize(norm_obs=False, norm_reward=True)``
 does, clipped at ``--clip-reward`` (default 10; DESIGN.md "Reward normalisation"); the logs keep the raw returns.
+``--eval-freq`` flies the current policy on the test scenarios (``--eval-scenarios``, default all seven; ``--eval-runs``
+episodes each) after the update that crosses a multiple of STEPS (``ppo.Evaluation``, SB3's EvalCallback): ``eval/*`` in the
+record and the logs, ``best_model.zip`` (by ``--eval-metric``) beside ``--save`` or else in ``--log-dir``, ``evaluations.npz`` in
+``--log-dir``.
 """
 from __future__ import annotations
 
@@ -66,13 +71,21 @@ def main():
     ap.add_argument("--norm-reward", action="store_true",
                     help="normalise the rollout's rewards by the running std of the discounted returns (VecNormalize)")
     ap.add_argument("--clip-reward", type=float, default=10.0, metavar="X", help="with --norm-reward: clip at +-X")
+    ap.add_argument("--eval-freq", type=int, default=0, metavar="STEPS",
+                    help="evaluate on the test scenarios every STEPS env steps (after the update that crosses them)")
+    ap.add_argument("--eval-runs", type=int, default=16, metavar="R", help="with --eval-freq: episodes per scenario")
+    ap.add_argument("--eval-scenarios", default=None, metavar="a,b,...",
+                    help="with --eval-freq: the scenarios (default: the seven test scenarios)")
+    ap.add_argument("--eval-metric", default="mean_reward", choices=("mean_reward", "success_rate"),
+                    help="with --eval-freq: what best_model.zip is the best by")
     a = ap.parse_args()
 
     import torch
 
     import drone2d_amd as d2
     from drone2d_amd.config import ENV_TRAIN_CONFIG
-    from drone2d_amd.ppo import PPO, Checkpoint, PPOConfig
+    from drone2d_amd.config import TEST_SCENARIOS
+    from drone2d_amd.ppo import PPO, Checkpoint, Evaluation, PPOConfig
 
     torch.cuda.set_device(0)
     kw = dict(ENV_TRAIN_CONFIG, scenario=a.scenario)
@@ -93,6 +106,12 @@ def main():
     if a.checkpoint_every > 0:
         ck_dir = os.path.dirname(os.path.abspath(a.save)) if a.save else "ppo_agents"
         ckpt = Checkpoint(a.checkpoint_every, ck_dir)
+    evaluation = None
+    if a.eval_freq > 0:
+        best_dir = os.path.dirname(os.path.abspath(a.save)) if a.save else a.log_dir
+        evaluation = Evaluation(a.eval_freq, scenarios=tuple(a.eval_scenarios.split(",")) if a.eval_scenarios else
+                                TEST_SCENARIOS, runs=a.eval_runs, seed=a.seed, metric=a.eval_metric, log_path=a.log_dir,
+                                best_model_save_path=best_dir)
     os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
     tag = ("_eager" if a.no_graph else "") + ("_autograd" if a.autograd else "") + ("_norm" if a.norm_reward else "")
     out = open(os.path.join(REPO, "gpurun_out", f"ppo{tag}.jsonl"), "w")
@@ -112,7 +131,7 @@ def main():
             # the reference's stage clock is the global step count (checkpoint names, :76-86)
             venv.refresh_curriculum(sim_num=algo.num_timesteps)
         rec = algo.learn(algo.num_timesteps + algo.cfg.n_steps * a.envs, checkpoint=ckpt, logger=logger,
-                         schedule_timesteps=horizon)[-1]
+                         schedule_timesteps=horizon, evaluation=evaluation)[-1]
         rec.update(update=u, wall_s=time.perf_counter() - t0)
         line = json.dumps({k: (round(v, 6) if isinstance(v, float) else v) for k, v in rec.items()})
         print(line, flush=True)
