@@ -199,6 +199,7 @@ __device__ __forceinline__ void store_tile(const MlpPair& P, int s0, int m, cons
         }
     }
 }
+template <bool TB>
 __device__ void rollout_epilogue(const d2d_ppo_rollout& R, int m, const float (*outs)[FM_TILES * FM_SPB]);
 // diagnostic builds only (-DD2D_PPO_STAMPS, tools/ubench_ppo_fwd.py --stamps): s_memtime at the
 // forward's phase boundaries, lane 0 of every wave, [workgroup][wave][8]
@@ -216,12 +217,19 @@ __device__ uint64_t* d2d_ppo_stamp_buf;
     } while (0)
 #endif
 // RO: the rollout step (d2d_ppo_rollout_step): rows are the envs in order (idx == nullptr), h1 / h2
-// stay on chip, the outputs go to LDS for the action / GAE epilogue instead of to P.net[].out
-template <bool RO>
+// stay on chip, the outputs go to LDS for the action / GAE epilogue instead of to P.net[].out.
+// TB (with RO, t >= 1): the truncation bootstrap (d2d_ppo_rollout_step_tb).  A workgroup with an env
+// that truncated at step t-1 runs the tile loop a second time on the terminal observations tobs
+// [n][27] -- same operands (w1r / w2r still in registers, w3s in LDS), same instructions, so the
+// value is the one the first pass gives the same 27 floats -- and leaves V(tobs) in outs[3] for the
+// epilogue.  Rows that did not truncate are zero-filled, never loaded: their tobs rows are stale.
+template <bool RO, bool TB = false>
 __device__ __forceinline__ void mlp_forward_mfma_body(const MlpPair& P, int m, const int64_t* __restrict__ idx,
                                                       const float* __restrict__ obs, float* __restrict__ xg,
                                                       const float* __restrict__ adv, double* __restrict__ ws,
-                                                      const d2d_ppo_rollout* R) {
+                                                      const d2d_ppo_rollout* R,
+                                                      const float* __restrict__ tobs = nullptr) {
+    static_assert(RO || !TB, "the truncation bootstrap belongs to the rollout step");
     // One LDS region, used first to stage both nets' W1 and W2 (read with coalesced loads: the
     // register operands below gathered straight from global memory touch 32 cache lines per
     // instruction, which made the kernel address-bound), then for the inputs and hidden tiles.
@@ -271,7 +279,15 @@ __device__ __forceinline__ void mlp_forward_mfma_body(const MlpPair& P, int m, c
         }
     }
     if (tid < FM_TILES * FM_SPB) rows[tid] = sb + tid < m ? (RO ? (int64_t)(sb + tid) : idx[sb + tid]) : -1;
-    __shared__ float outs[RO ? 3 : 1][FM_TILES * FM_SPB];  // RO: mean (2 rows) and value per sample
+    // RO: mean (2 rows) and value per sample; TB: and the value of the sample's terminal observation
+    __shared__ float outs[RO ? (TB ? 4 : 3) : 1][FM_TILES * FM_SPB];
+    __shared__ unsigned long long tbmask;  // TB: bit l = env sb + l truncated at step t-1
+    if constexpr (TB) {
+        if (tid < FM_TILES * FM_SPB) {  // wave 0 ballots; the flag is uniform over the workgroup after the barrier
+            const unsigned long long b = __ballot(sb + tid < m && R->prev_trunc[sb + tid] != 0);
+            if (tid == 0) tbmask = b;
+        }
+    }
     const float b1 = N.b1[j0 + ci], b2 = N.b2[j0 + ci];
     __syncthreads();  // weights staged, rows
     PPO_STAMP(1);
@@ -315,55 +331,85 @@ __device__ __forceinline__ void mlp_forward_mfma_body(const MlpPair& P, int m, c
             }
         }
     }
-    for (int tile = 0; tile < FM_TILES; ++tile) {
-        const int s0 = sb + tile * FM_SPB;
-        __syncthreads();  // staging done / the previous tile's outputs have read hs
-        PPO_STAMP(3 + tile);
-        // layer 1 (k = 27 inputs, padded to 28)
-        f32x16 acc = {};
+    // TB: pass 1 is the truncated envs' terminal observations through the value net
+    for (int pass = 0; pass < (TB ? 2 : 1); ++pass) {
+        unsigned long long tmask = ~0ull;
+        // pass 1 needs only the value; the policy net's waves keep the barriers and skip the arithmetic
+        const bool work = !TB || pass == 0 || net == 1;
+        if constexpr (TB) {
+            if (pass == 1) {
+                tmask = tbmask;
+                if (tmask == 0) break;  // (uniform) nothing truncated in this workgroup: no second pass
+                // xs is free (the last barrier every wave passed follows its last read of xs); its
+                // padding column is still 0
 #pragma unroll
-        for (int t = 0; t < (OBS + 1) / 2; ++t)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[tile * FM_SPB + ci][2 * t + h], w1r[t], acc, 0, 0, 0);
-#pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int i = (v & 3) + 8 * (v >> 2) + 4 * h;  // sample of register v (C/D map)
-            const float y = ftanh(acc[v] + b1);
-            hs[net][i][j0 + ci] = y;
+                for (int c = 0; c < NI; ++c) {
+                    const int e = c * 256 + tid, sl = e / OBS;
+                    if (e < NX) xs[sl][e % OBS] = (tmask >> sl) & 1 ? tobs[(size_t)sb * OBS + e] : 0.0f;
+                }
+            }
         }
-        __syncthreads();
-        if (!RO) store_tile(P, s0, m, hs, tid, false);
-        // layer 2
-        acc = f32x16{};
+        for (int tile = 0; tile < FM_TILES; ++tile) {
+            const int s0 = sb + tile * FM_SPB;
+            if constexpr (TB) {
+                if (((tmask >> (tile * FM_SPB)) & 0xffffffffull) == 0) continue;  // (uniform) no truncated row in the tile
+            }
+            __syncthreads();  // staging done / the previous tile's outputs have read hs
+            PPO_STAMP(3 + tile);
+            // layer 1 (k = 27 inputs, padded to 28)
+            f32x16 acc = {};
+            if (work) {
 #pragma unroll
-        for (int t = 0; t < HID / 2; ++t)
-            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(hs[net][ci][2 * t + h], w2r[t], acc, 0, 0, 0);
-        __syncthreads();  // every wave has read h1 before h2 overwrites it
+                for (int t = 0; t < (OBS + 1) / 2; ++t)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(xs[tile * FM_SPB + ci][2 * t + h], w1r[t], acc, 0, 0, 0);
 #pragma unroll
-        for (int v = 0; v < 16; ++v) {
-            const int i = (v & 3) + 8 * (v >> 2) + 4 * h;
-            const float y = ftanh(acc[v] + b2);
-            hs[net][i][j0 + ci] = y;
-        }
-        __syncthreads();
-        if (!RO) store_tile(P, s0, m, hs, tid, true);
-        // output layers: thread t -> (output row t / 32 of both nets' od0 + od1 rows, sample t % 32),
-        // weights and biases from LDS
-        if (tid < (od0 + P.net[1].od) * FM_SPB) {
-            const int orow = tid / FM_SPB, sl = tid % FM_SPB, i = s0 + sl, on = orow >= od0;
-            const int r = orow - on * od0;
-            float o = w3s[orow][HID];
+                for (int v = 0; v < 16; ++v) {
+                    const int i = (v & 3) + 8 * (v >> 2) + 4 * h;  // sample of register v (C/D map)
+                    const float y = ftanh(acc[v] + b1);
+                    hs[net][i][j0 + ci] = y;
+                }
+            }
+            __syncthreads();
+            if (!RO) store_tile(P, s0, m, hs, tid, false);
+            // layer 2
+            acc = f32x16{};
+            if (work) {
+#pragma unroll
+                for (int t = 0; t < HID / 2; ++t)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(hs[net][ci][2 * t + h], w2r[t], acc, 0, 0, 0);
+            }
+            __syncthreads();  // every wave has read h1 before h2 overwrites it
+            if (work) {
+#pragma unroll
+                for (int v = 0; v < 16; ++v) {
+                    const int i = (v & 3) + 8 * (v >> 2) + 4 * h;
+                    const float y = ftanh(acc[v] + b2);
+                    hs[net][i][j0 + ci] = y;
+                }
+            }
+            __syncthreads();
+            if (!RO) store_tile(P, s0, m, hs, tid, true);
+            // output layers: thread t -> (output row t / 32 of both nets' od0 + od1 rows, sample t % 32),
+            // weights and biases from LDS
+            if (tid < (od0 + P.net[1].od) * FM_SPB && (!TB || pass == 0 || tid >= od0 * FM_SPB)) {
+                const int orow = tid / FM_SPB, sl = tid % FM_SPB, i = s0 + sl, on = orow >= od0;
+                const int r = orow - on * od0;
+                float o = w3s[orow][HID];
 #pragma unroll 16
-            for (int j = 0; j < HID; ++j) o += w3s[orow][j] * hs[on][sl][j];
-            if (RO)
-                outs[orow][tile * FM_SPB + sl] = o;
-            else if (i < m)
-                P.net[on].out[(size_t)i * P.net[on].od + r] = o;
+                for (int j = 0; j < HID; ++j) o += w3s[orow][j] * hs[on][sl][j];
+                if constexpr (TB)
+                    outs[pass ? 3 : orow][tile * FM_SPB + sl] = o;
+                else if (RO)
+                    outs[orow][tile * FM_SPB + sl] = o;
+                else if (i < m)
+                    P.net[on].out[(size_t)i * P.net[on].od + r] = o;
+            }
         }
     }
     PPO_STAMP(5);
     if (RO) {
         __syncthreads();
-        if (tid < FM_TILES * FM_SPB) rollout_epilogue(*R, m, outs);  // wave 0: one env per lane
+        if (tid < FM_TILES * FM_SPB) rollout_epilogue<TB>(*R, m, outs);  // wave 0: one env per lane
     }
     PPO_STAMP(6);
 }
@@ -377,7 +423,10 @@ __global__ __launch_bounds__(256) void mlp_forward_mfma_kernel(MlpPair P, int m,
 
 // The rollout step's epilogue, lane l of wave 0 = env sb + l.  Operation order as the torch
 // restatement (ppo.py _rollout_body / compute_gae), without contraction: the GAE recursion gives the
-// bits torch computes from the same rewards, values and dones.
+// bits torch computes from the same rewards, values and dones.  TB: outs[3] holds V(terminal obs) of
+// the envs that truncated at step t-1; their reward becomes rew + gamma V (two roundings, torch's
+// rew + gamma * tv), selected, never blended: the other envs' outs[3] is never read.
+template <bool TB>
 __device__ void rollout_epilogue(const d2d_ppo_rollout& R, int m, const float (*outs)[FM_TILES * FM_SPB]) {
 #pragma clang fp contract(off)
     const int l = threadIdx.x, i = blockIdx.x * (FM_TILES * FM_SPB) + l, n = m, t = R.t, T = R.T;
@@ -389,6 +438,12 @@ __device__ void rollout_epilogue(const d2d_ppo_rollout& R, int m, const float (*
         if (ok) {
             rew_p = R.prev_rew[i];
             d_p = (R.prev_term[i] | R.prev_trunc[i]) != 0;
+            if constexpr (TB) {
+                if (R.prev_trunc[i] != 0) {
+                    const float gv = R.gamma * outs[3][l];
+                    rew_p = rew_p + gv;
+                }
+            }
             R.rew_buf[(size_t)(t - 1) * n + i] = rew_p;
             R.done_buf[(size_t)(t - 1) * n + i] = d_p;
             if (d_p) {
@@ -439,6 +494,11 @@ __device__ void rollout_epilogue(const d2d_ppo_rollout& R, int m, const float (*
 }
 __global__ __launch_bounds__(256) void rollout_step_kernel(MlpPair P, int m, float* __restrict__ xg, d2d_ppo_rollout R) {
     mlp_forward_mfma_body<true>(P, m, nullptr, R.obs, xg, nullptr, nullptr, &R);
+}
+// d2d_ppo_rollout_step_tb (t >= 1): the same body, instantiated with the truncation bootstrap
+__global__ __launch_bounds__(256) void rollout_step_tb_kernel(MlpPair P, int m, float* __restrict__ xg, d2d_ppo_rollout R,
+                                                              const float* __restrict__ tobs) {
+    mlp_forward_mfma_body<true, true>(P, m, nullptr, R.obs, xg, nullptr, nullptr, &R, tobs);
 }
 
 // ---------------------------------------------------------------- per-epoch minibatch shuffles
@@ -1447,7 +1507,9 @@ int32_t d2d_ppo_permute(int64_t n, int32_t n_perm, uint64_t seed, uint64_t* coun
     return rc(hipGetLastError());
 }
 
-int32_t d2d_ppo_rollout_step(const d2d_ppo_rollout* r, const float* const* weights, void* stream) {
+int32_t d2d_ppo_tb_version(void) { return D2D_PPO_TB_VERSION; }
+
+static int32_t rollout_step(const d2d_ppo_rollout* r, const float* tobs, const float* const* weights, void* stream) {
     if (r == nullptr || weights == nullptr) return (int32_t)hipErrorInvalidValue;
     const d2d_ppo_rollout& R = *r;
     if (R.n <= 0) return 0;
@@ -1465,9 +1527,19 @@ int32_t d2d_ppo_rollout_step(const d2d_ppo_rollout* r, const float* const* weigh
     float* none[10] = {};
     MlpPair P = make_pair(weights, none);
     float* xg = R.t < R.T ? R.obs_buf + (size_t)R.t * R.n * OBS : nullptr;
-    hipLaunchKernelGGL(rollout_step_kernel, dim3((R.n + FM_TILES * FM_SPB - 1) / (FM_TILES * FM_SPB)), dim3(256), 0,
-                       (hipStream_t)stream, P, R.n, xg, R);
+    const dim3 grid((R.n + FM_TILES * FM_SPB - 1) / (FM_TILES * FM_SPB));
+    if (tobs != nullptr && R.t > 0)
+        hipLaunchKernelGGL(rollout_step_tb_kernel, grid, dim3(256), 0, (hipStream_t)stream, P, R.n, xg, R, tobs);
+    else
+        hipLaunchKernelGGL(rollout_step_kernel, grid, dim3(256), 0, (hipStream_t)stream, P, R.n, xg, R);
     return rc(hipGetLastError());
+}
+int32_t d2d_ppo_rollout_step(const d2d_ppo_rollout* r, const float* const* weights, void* stream) {
+    return rollout_step(r, nullptr, weights, stream);
+}
+int32_t d2d_ppo_rollout_step_tb(const d2d_ppo_rollout* r, const float* prev_term_obs, const float* const* weights,
+                                void* stream) {
+    return rollout_step(r, prev_term_obs, weights, stream);
 }
 
 int32_t d2d_ppo_mlp_backward(int32_t m, const int64_t* idx, const float* act, const float* old_logp, const float* adv,

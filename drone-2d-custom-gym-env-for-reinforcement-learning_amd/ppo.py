@@ -260,8 +260,8 @@ class PPO:
         f64 = dict(dtype=torch.float64, device=dev)
         # time-limit truncations are bootstrapped with V(terminal obs); the reference never truncates
         self._truncates = bool(getattr(getattr(self.venv, "cfg", None), "timeup_truncates", 1))
-        # the fused rollout: the HIP env batch, no truncation bootstrap (its extra value pass stays in torch)
-        self._fused = bool(self._hip and isinstance(self.venv, Drone2dVecEnv) and not self._truncates)
+        # the fused rollout: the HIP env batch (with _truncates its step is d2d_ppo_rollout_step_tb)
+        self._fused = bool(self._hip and isinstance(self.venv, Drone2dVecEnv))
         self._ro = {"val": torch.empty(T, N, device=dev), "rew": torch.empty(T, N, device=dev),
                     "done": torch.empty(T, N, dtype=torch.bool, device=dev),
                     "start0": torch.empty(N, dtype=torch.bool, device=dev),
@@ -321,7 +321,10 @@ class PPO:
         """_rollout_body as T + 1 libd2d_ppo.so launches around the T env steps: step t's launch runs
         both MLPs on the env's observation tensor, samples and stores the action, log-density and
         value, copies the observations into the flat buffer and records step t-1's reward / done /
-        episode statistics; the last one adds the bootstrap value and GAE (d2d_ppo_rollout_step)."""
+        episode statistics; the last one adds the bootstrap value and GAE (d2d_ppo_rollout_step).  With
+        ``_truncates`` the launch is d2d_ppo_rollout_step_tb, which also reads step t-1's terminal
+        observations and adds gamma V(terminal obs) to the recorded reward of the envs that truncated --
+        after the normaliser has rewritten the reward, SB3's order around a VecNormalize."""
         from . import abi
 
         R, T, N, lib = self._ro, self.cfg.n_steps, self.n_envs, self.manual.lib
@@ -335,12 +338,15 @@ class PPO:
                           logp_buf=ptr(logp_buf), val_buf=ptr(R["val"]), rew_buf=ptr(R["rew"]),
                           done_buf=ptr(R["done"]), start0=ptr(R["start0"]), act_env=ptr(R["act_env"]),
                           adv_buf=ptr(adv_buf), ret_buf=ptr(ret_buf), stats=ptr(R["stats"]))
-        obs = R["obs_cur"]
+        obs, tobs = R["obs_cur"], None
         for t in range(T + 1):
             r.t = t
             r.obs = ptr(obs)
             r.noise = ptr(R["noise"][t]) if t < T else None
-            _ok(lib.d2d_ppo_rollout_step(r, wptr, st), "d2d_ppo_rollout_step")  # (passed by reference: argtypes)
+            if self._truncates:
+                _ok(lib.d2d_ppo_rollout_step_tb(r, ptr(tobs), wptr, st), "d2d_ppo_rollout_step_tb")
+            else:
+                _ok(lib.d2d_ppo_rollout_step(r, wptr, st), "d2d_ppo_rollout_step")  # (passed by reference: argtypes)
             if t < T:
                 obs, rew, term, trunc, info = self.venv.step(R["act_env"])
                 if self.monitor is not None:
@@ -348,6 +354,7 @@ class PPO:
                 if self.normalizer is not None:  # (the monitor and the episode statistics read info: raw)
                     rew = self.normalizer.step(rew, term, trunc)
                 r.prev_rew, r.prev_term, r.prev_trunc, r.prev_info = ptr(rew), ptr(term), ptr(trunc), ptr(info)
+                tobs = self.venv.terminal_obs  # of this step: double-buffered like the other outputs
         if self.monitor is not None:
             self.monitor.flush()
         R["obs_cur"] = obs  # T even: the same double-buffer slot as at the start

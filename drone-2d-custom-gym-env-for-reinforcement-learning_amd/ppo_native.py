@@ -25,6 +25,7 @@ class D2DPPOCtl(C.Structure):
 
 ABI_VERSION = 6
 PPO_CTL_VERSION = 1
+PPO_TB_VERSION = 1
 
 _vp, _i32, _i64, _f32 = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 # every entry point returns a hipError_t: name -> (restype, argtypes)
@@ -52,6 +53,9 @@ SIGNATURES = {name: (C.c_int32, args) for name, args in {
     "d2d_ppo_fused_grad_ctl": [_i32, *[_vp] * 9, _i32, _f32, _vp, _vp, _i32, _vp, _vp, _vp, _vp],
     "d2d_ppo_grad_reduce_ctl": [_i32, _i32, _vp, _vp, _i32, _vp, _i32, _vp, _f32, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
     "d2d_ppo_adam_ctl": [_i32, _vp, _vp, _vp, _vp, _vp, _f32, _f32, _f32, _f32, _vp, _vp],
+    # the rollout step with the time-limit bootstrap (additive to ABI v6; versioned by d2d_ppo_tb_version)
+    "d2d_ppo_tb_version": [],
+    "d2d_ppo_rollout_step_tb": [C.POINTER(D2DPPORollout), _vp, _vp, _vp],
 }.items()}
 
 _PPO_LIB = None
@@ -69,6 +73,8 @@ def ppo_native():
                            "libd2d_ppo.so ABI mismatch")
         _native.check_version(lib, path, "d2d_ppo_ctl_version", PPO_CTL_VERSION, RuntimeError,
                               "libd2d_ppo.so control-block version mismatch")
+        _native.check_version(lib, path, "d2d_ppo_tb_version", PPO_TB_VERSION, RuntimeError,
+                              "libd2d_ppo.so truncation-bootstrap version mismatch")
         _PPO_LIB = lib
     return _PPO_LIB
 

@@ -109,7 +109,8 @@ int32_t d2d_ppo_permute(int64_t n, int32_t n_perm, uint64_t seed, uint64_t* coun
  * statistics of step t-1.  t == T: the bootstrap value of obs, step T-1's env outputs, then
  * RolloutBuffer.compute_returns_and_advantage (GAE(gamma, gae_lambda) with the episode starts, same
  * operation order as the torch restatement) into adv_buf / ret_buf.  Time-limit bootstrapping of
- * truncated episodes is not done here (the reference never truncates). */
+ * truncated episodes is d2d_ppo_rollout_step_tb's (declared with the step, below); this entry point
+ * records the env's reward as it is (the reference never truncates). */
 /* The minibatch gradient in one launch (ABI v5): what d2d_ppo_mlp_forward_adv + d2d_ppo_mlp_backward +
  * d2d_ppo_wgrad compute, with every per-sample activation and gradient kept on chip.  Workgroup
  * (x, net) handles the 64-sample chunks x, x + R, ... (R = d2d_ppo_fused_rows(m)) of rows idx[0..m) and
@@ -237,6 +238,36 @@ typedef struct d2d_ppo_rollout {
                                 step t-1 */
 } d2d_ppo_rollout;
 int32_t d2d_ppo_rollout_step(const d2d_ppo_rollout* r, const float* const* weights, void* stream);
+
+/* ---------------------------------------------------------------------------------------------------
+ * Time-limit bootstrap inside the rollout step (additive to ABI v6; a version of its own).
+ *
+ * d2d_ppo_rollout_step with one difference: for t >= 1, env i with prev_trunc[i] != 0 records
+ * rew = prev_rew[i] + gamma * V(prev_term_obs[i]) instead of prev_rew[i] -- in rew_buf row t-1 and, at
+ * t == T, in the GAE recursion's step T-1 (SB3 2.1 collect_rollouts: rewards[idx] += gamma *
+ * predict_values(terminal_observation) where TimeLimit.truncated).  prev_term_obs [n][27] is the env's
+ * terminal-observation tensor of step t-1 (d2d_step's term_obs).
+ *
+ *  - One launch, ordered on the stream, no allocation and no synchronisation: the bootstrap is a second
+ *    pass through the tile loop inside the same workgroup (a second instantiation of the step's kernel).
+ *  - V(prev_term_obs[i]) is bit for bit the value this kernel's value head writes to val_buf when the
+ *    same 27 floats arrive as an ordinary obs row: the same matrix-core tiles, tanh and 64-term output
+ *    loop.  It does not depend on n, on the row's place or on its neighbours.
+ *  - rew = prev_rew + (gamma * V): two float32 roundings, no contraction (torch's rew + gamma * tv).
+ *  - Selected, never blended: rows with prev_trunc == 0 record prev_rew unchanged, bit for bit.  Their
+ *    prev_term_obs rows are stale (the env writes finished envs' rows only) and may hold anything, NaN
+ *    included; they are not loaded, and nothing of them reaches an output.
+ *  - A workgroup none of whose 64 envs truncated at step t-1 does no second pass (the decision is
+ *    uniform over the workgroup); within one that does, a 32-env tile without a truncated env is skipped.
+ *  - The condition is prev_trunc != 0, whatever prev_term holds (the env never sets both).
+ *  - done_buf, stats (episode counts and the raw info returns), start0, act_*, logp_buf, val_buf and
+ *    obs_buf are what d2d_ppo_rollout_step writes.
+ *  - prev_term_obs == NULL or t == 0: exactly d2d_ppo_rollout_step (the same kernel instantiation, the
+ *    same bits).  hipErrorInvalidValue, with nothing launched, for whatever d2d_ppo_rollout_step rejects. */
+#define D2D_PPO_TB_VERSION 1
+int32_t d2d_ppo_tb_version(void);
+int32_t d2d_ppo_rollout_step_tb(const d2d_ppo_rollout* r, const float* prev_term_obs /* [n][27] */,
+                                const float* const* weights, void* stream);
 
 #ifdef __cplusplus
 }

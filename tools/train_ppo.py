@@ -5,7 +5,7 @@
                               [--save AGENT.zip] [--checkpoint-every STEPS] [--resume AGENT.zip]
                               [--log-dir DIR [--no-tensorboard]]
                               [--lr-end LR] [--clip-range-end C] [--clip-range-vf C] [--target-kl KL]
-                              [--norm-reward [--clip-reward X]]
+                              [--norm-reward [--clip-reward X]] [--timeup-truncates [--episode-steps K]]
                               [--eval-freq STEPS [--eval-runs R] [--eval-scenarios a,b,...] [--eval-metric M]]
 
 One JSON line per update (timesteps, mean finished-episode return, losses, env-steps/s including
@@ -24,6 +24,9 @@ event file, ``env_train_config.txt`` and ``rl_config.txt`` there (drone2d_amd.tr
 ``--target-kl`` (``inf``: log approx_kl only) select PPO's control path (PPOConfig; DESIGN.md "PPO control").
 ``--norm-reward`` normalises the rewards the rollout records as SB3's ``VecNormalize(norm_obs=False, norm_reward=True)``
 does, clipped at ``--clip-reward`` (default 10; DESIGN.md "Reward normalisation"); the logs keep the raw returns.
+``--timeup-truncates`` builds the batch with ``timeup_truncates=True``: the time-up is a truncation, and the rollout adds
+``gamma V(terminal obs)`` to a truncated step's reward inside its fused step (DESIGN.md "Truncation bootstrap");
+``--episode-steps`` sets the env's time limit (the config's ``n_steps``, 1 100 by default).
 ``--eval-freq`` flies the current policy on the test scenarios (``--eval-scenarios``, default all seven; ``--eval-runs``
 episodes each) after the update that crosses a multiple of STEPS (``ppo.Evaluation``, SB3's EvalCallback): ``eval/*`` in the
 record and the logs, ``best_model.zip`` (by ``--eval-metric``) beside ``--save`` or else in ``--log-dir``, ``evaluations.npz`` in
@@ -71,6 +74,9 @@ def main():
     ap.add_argument("--norm-reward", action="store_true",
                     help="normalise the rollout's rewards by the running std of the discounted returns (VecNormalize)")
     ap.add_argument("--clip-reward", type=float, default=10.0, metavar="X", help="with --norm-reward: clip at +-X")
+    ap.add_argument("--timeup-truncates", action="store_true",
+                    help="report the time-up as a truncation and bootstrap it with the value of the terminal observation")
+    ap.add_argument("--episode-steps", type=int, default=None, metavar="K", help="the env's time limit (config n_steps)")
     ap.add_argument("--eval-freq", type=int, default=0, metavar="STEPS",
                     help="evaluate on the test scenarios every STEPS env steps (after the update that crosses them)")
     ap.add_argument("--eval-runs", type=int, default=16, metavar="R", help="with --eval-freq: episodes per scenario")
@@ -93,7 +99,9 @@ def main():
         kw.update(mode="curriculum", scenario="curriculum", sim_num=0, curriculum_seed=a.seed)
         if a.pool > 0:  # a host-generated pool; --pool 0: every reset on a fresh device-generated scenario
             kw["curriculum_pool"] = a.pool
-    venv = d2.Drone2dVecEnv(a.envs, seed=a.seed, **kw)
+    if a.episode_steps is not None:
+        kw["n_steps"] = a.episode_steps
+    venv = d2.Drone2dVecEnv(a.envs, seed=a.seed, timeup_truncates=a.timeup_truncates, **kw)
     cfg = PPOConfig.gpu_defaults(n_steps=a.n_steps, batch_size=a.batch, n_epochs=a.epochs,
                                  learning_rate_end=a.lr_end, clip_range_end=a.clip_range_end,
                                  clip_range_vf=a.clip_range_vf, target_kl=a.target_kl, norm_reward=a.norm_reward,
@@ -113,7 +121,8 @@ def main():
                                 TEST_SCENARIOS, runs=a.eval_runs, seed=a.seed, metric=a.eval_metric, log_path=a.log_dir,
                                 best_model_save_path=best_dir)
     os.makedirs(os.path.join(REPO, "gpurun_out"), exist_ok=True)
-    tag = ("_eager" if a.no_graph else "") + ("_autograd" if a.autograd else "") + ("_norm" if a.norm_reward else "")
+    tag = ("_eager" if a.no_graph else "") + ("_autograd" if a.autograd else "") + ("_norm" if a.norm_reward else "") + \
+          ("_trunc" if a.timeup_truncates else "")
     out = open(os.path.join(REPO, "gpurun_out", f"ppo{tag}.jsonl"), "w")
     logger = None
     if a.log_dir:
