@@ -32,6 +32,12 @@ RENDER_SRC = os.path.join(PKG_DIR, "csrc", "render", "d2d_render.hip")
 RENDER_HDRS = [os.path.join(PKG_DIR, "csrc", "render", "d2d_raster.h"), os.path.join(PKG_DIR, "csrc", "d2d_pmath.h"),
                os.path.join(REPO, "include", "d2d_render.h"), os.path.join(REPO, "include", "drone2d.h")]
 RENDER_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_render.so")
+# the text overlay, angle arcs and drone shades (include/d2d_hud.h): a library beside the renderer, built
+# around the renderer's own headers (the primitive list and the tile walk of d2d_raster.h)
+HUD_SRC = os.path.join(PKG_DIR, "csrc", "hud", "d2d_hud.hip")
+HUD_HDRS = [os.path.join(PKG_DIR, "csrc", "hud", "d2d_hud_core.h"), os.path.join(PKG_DIR, "csrc", "hud", "d2d_font.h"),
+            os.path.join(REPO, "include", "d2d_hud.h"), *RENDER_HDRS]
+HUD_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_hud.so")
 # the fused evaluation step (include/d2d_eval.h), a library of its own under csrc/eval/
 EVAL_SRC = os.path.join(PKG_DIR, "csrc", "eval", "d2d_eval.hip")
 EVAL_HDRS = [os.path.join(PKG_DIR, "csrc", "eval", "d2d_eval_math.h"), os.path.join(REPO, "include", "d2d_eval.h")]
@@ -100,6 +106,14 @@ def build_render(force: bool = False, verbose: bool = False) -> str:
     return RENDER_OUT
 
 
+def build_hud(force: bool = False, verbose: bool = False) -> str:
+    """The HUD renderer (libd2d_hud.so), with the renderer's flags (-ffp-contract=off: host twins and
+    kernels round alike).  Compiled by ``build()`` or by the first HUD frame that finds it missing."""
+    if force or needs_build(HUD_OUT, HUD_SRC, HUD_HDRS):
+        _compile(HUD_SRC, HUD_OUT, verbose)
+    return HUD_OUT
+
+
 def build_eval(force: bool = False, verbose: bool = False) -> str:
     """The evaluation step (libd2d_eval.so), with the PPO library's flags (float32 arithmetic, FMAs
     contracted within an expression).  Compiled by ``build()`` or by the first evaluation that finds
@@ -130,7 +144,7 @@ def build_norm(force: bool = False, verbose: bool = False) -> str:
 
 def build(force: bool = False, verbose: bool = False, exact: bool = False) -> str:
     """The in-tree libraries: the env (libdrone2d_hip.so: every mode, one scenario layout), the PPO
-    update kernels (libd2d_ppo.so), the renderer (libd2d_render.so), the evaluation step
+    update kernels (libd2d_ppo.so), the renderer (libd2d_render.so) and its HUD (libd2d_hud.so), the evaluation step
     (libd2d_eval.so), the episode monitor (libd2d_monitor.so), reward normalisation (libd2d_norm.so)
     and, with ``exact``, the env's exact-trig build."""
     stale = os.path.join(PKG_DIR, "_lib", "libdrone2d_hip_rm.so")  # rounds 1-3's second layout build
@@ -143,6 +157,7 @@ def build(force: bool = False, verbose: bool = False, exact: bool = False) -> st
     if force or needs_build(PPO_OUT, PPO_SRC, PPO_HDRS):
         _compile(PPO_SRC, PPO_OUT, verbose, PPO_FLAGS)
     build_render(force, verbose)
+    build_hud(force, verbose)
     build_eval(force, verbose)
     build_monitor(force, verbose)
     build_norm(force, verbose)

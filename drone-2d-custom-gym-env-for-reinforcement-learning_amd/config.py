@@ -3,7 +3,9 @@
 ``Drone2dEnv`` in the reference reads 29 required keys by subscript
 (``drone_2d_env.py:34-66``), so a missing key raises ``KeyError``; ``make_cfg`` keeps that
 behaviour.  ``render_path`` makes ``Drone2dEnv`` keep its flight path (and draw it as the trail of
-``render(mode="rgb_array")``); the other render keys are accepted and ignored (no window is opened), and
+``render(mode="rgb_array")``); ``render_text``, ``render_shade`` and ``shade_distance`` decide what
+``render(mode="rgb_array", hud=True)`` adds to it (the text overlay, the shades; drone2d_amd.hud) and are
+ignored without ``hud``; ``render_sim`` is accepted and ignored (no window is opened), and
 ``initial_throw`` / ``n_fall_steps`` are accepted and inert exactly as in the reference, where
 ``initial_movement()`` (``drone_2d_env.py:917-946``) is never called.
 """

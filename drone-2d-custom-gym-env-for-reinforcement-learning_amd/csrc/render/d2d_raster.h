@@ -6,6 +6,8 @@
  *   covers          the fp32 coverage predicate (add, mul, div, compare only)
  *   render_host ... the CPU twins: the same list, the same predicate, the same last-wins resolve
  * Compile with -ffp-contract=off on both sides: host and device then round identically.
+ * A fourth, for the device alone (at the end, under __HIPCC__): the 64 x 4 tile walk over a primitive
+ * list, which d2d_render.hip and csrc/hud/d2d_hud.hip both instantiate.
  */
 #ifndef D2D_RASTER_H
 #define D2D_RASTER_H
@@ -449,5 +451,118 @@ inline void plot_paths_host(const d2dr_view* view, const d2d_scn* scn, const flo
     }
     resolve_host(prims, v, ids.data(), rgb, out);
 }
+
+#if defined(__HIPCC__)
+/* ---- the tile walk (device only) ------------------------------------------------------------------
+ * One workgroup of NT lanes resolves one 64 x 4 pixel tile of one frame: one wave per pixel row.  Shared
+ * by every library that rasterises a primitive list (libd2d_render.so, libd2d_hud.so): a kernel declares
+ * one TileLds, takes its Tile from tile_of(), and either calls walk_tile() -- templated on what differs
+ * between the lists: the list's length and the colour of a pixel no primitive covers -- or strings
+ * scan_range() calls together itself (the plot) and ends with store_tile(). */
+constexpr int TW = 64, TH = 4, NT = TW * TH;
+
+struct TileLds {
+    Prim prim[NT];
+    int32_t wcnt[NT / 64];
+    uint8_t rgb[TH][TW * 3];
+};
+
+struct Tile {
+    int32_t tx0, ty0, tc1, tr1;  /* first column / row; last column / row inside the picture */
+    int32_t row, col;            /* this lane's pixel */
+    float x, y;                  /* its centre */
+    bool inside;
+};
+
+__device__ __forceinline__ Tile tile_of(const View& v) {
+    const int32_t t = (int32_t)threadIdx.x, lane = t & 63, w = t >> 6;
+    const int32_t tiles_x = (v.W + TW - 1) / TW;
+    Tile q;
+    q.tx0 = ((int32_t)blockIdx.x % tiles_x) * TW, q.ty0 = ((int32_t)blockIdx.x / tiles_x) * TH;
+    q.col = q.tx0 + lane, q.row = q.ty0 + w;
+    q.tc1 = (q.tx0 + TW - 1 < v.W - 1) ? q.tx0 + TW - 1 : v.W - 1;
+    q.tr1 = (q.ty0 + TH - 1 < v.H - 1) ? q.ty0 + TH - 1 : v.H - 1;
+    q.inside = q.col <= q.tc1 && q.row <= q.tr1;
+    q.x = pixel_x(v, q.col), q.y = pixel_y(v, q.row);
+    return q;
+}
+
+/* Primitives [lo, hi) of the list, top first, 256 at a time: cull against the tile, compact the
+ * survivors into LDS in list order, then every unresolved pixel scans them. */
+__device__ __forceinline__ void scan_range(const Prim* __restrict__ fp, int32_t lo, int32_t hi, const Tile& q, bool& hit,
+                                           uint32_t& colour, TileLds& lds) {
+    const int32_t t = (int32_t)threadIdx.x, lane = t & 63, w = t >> 6;
+    for (int32_t base = hi; base > lo; base -= NT) {
+        if (!__syncthreads_or(hit ? 0 : 1)) break;  /* every pixel of the tile has its colour (uniform) */
+        const int32_t idx = base - 1 - t;
+        /* the primitive as three 16-byte words (a.xyzw, b.xy = p[0..5]; b.z = rgbk; b.w, c.xyz = c0, c1, r0, r1) */
+        const uint4* src = reinterpret_cast<const uint4*>(fp + (idx >= lo ? idx : lo));
+        const uint4 qa = src[0], qb = src[1], qc = src[2];
+        const bool keep = idx >= lo && (qb.z >> 24) != K_NONE && (int32_t)qb.w <= q.tc1 && (int32_t)qc.x >= q.tx0 &&
+                          (int32_t)qc.y <= q.tr1 && (int32_t)qc.z >= q.ty0;
+        const unsigned long long b = __ballot(keep);
+        if (lane == 0) lds.wcnt[w] = __popcll(b);
+        __syncthreads();
+        int32_t off = 0, total = 0;
+#pragma unroll
+        for (int k = 0; k < NT / 64; ++k) {
+            const int32_t c = lds.wcnt[k];
+            off += (k < w) ? c : 0;
+            total += c;
+        }
+        if (keep) {
+            uint4* dst = reinterpret_cast<uint4*>(lds.prim + off + __popcll(b & ((1ull << lane) - 1ull)));
+            dst[0] = qa, dst[1] = qb, dst[2] = qc;
+        }
+        __syncthreads();
+        if (!hit)
+            for (int32_t k = 0; k < total; ++k)
+                if (covers(lds.prim[k], q.row, q.col, q.x, q.y)) {
+                    colour = lds.prim[k].rgbk;
+                    hit = true;
+                    break;
+                }
+    }
+}
+
+/* The tile's RGB bytes, staged in LDS, leave as dwords (bytes only at a row's unaligned ends). */
+__device__ __forceinline__ void store_tile(const View& v, const Tile& q, int32_t f, uint32_t colour, TileLds& lds,
+                                           uint8_t* __restrict__ out) {
+    const int32_t t = (int32_t)threadIdx.x, lane = t & 63, w = t >> 6;
+    if (q.inside) {
+        lds.rgb[w][3 * lane] = (uint8_t)(colour & 255u);
+        lds.rgb[w][3 * lane + 1] = (uint8_t)((colour >> 8) & 255u);
+        lds.rgb[w][3 * lane + 2] = (uint8_t)((colour >> 16) & 255u);
+    }
+    __syncthreads();
+    if (q.row > q.tr1) return;
+    /* wave w stores pixel row `row`: bytes up to the first 4-byte boundary, dwords, bytes after the last */
+    const int32_t nbytes = 3 * (q.tc1 - q.tx0 + 1);
+    uint8_t* g = out + (((size_t)f * (size_t)v.H + (size_t)q.row) * (size_t)v.W + (size_t)q.tx0) * 3;
+    int32_t head = (int32_t)((4u - (uint32_t)((uintptr_t)g & 3u)) & 3u);
+    head = head < nbytes ? head : nbytes;
+    const int32_t ndw = (nbytes - head) >> 2, tail0 = head + 4 * ndw;
+    if (lane < head) g[lane] = lds.rgb[w][lane];
+    if (lane < ndw) {
+        const uint8_t* s = &lds.rgb[w][head + 4 * lane];
+        *reinterpret_cast<uint32_t*>(g + head + 4 * lane) =
+            (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
+    }
+    if (lane < nbytes - tail0) g[tail0 + lane] = lds.rgb[w][tail0 + lane];
+}
+
+/* A frame whose picture is its list and nothing else: `len(f)` primitives at fp, and `uncovered(row,
+ * col)` for a pixel that none of them covers (evaluated for such pixels only). */
+template <class Len, class Uncovered>
+__device__ __forceinline__ void walk_tile(const Prim* __restrict__ fp, const View& v, int32_t f, Len len,
+                                          Uncovered uncovered, TileLds& lds, uint8_t* __restrict__ out) {
+    const Tile q = tile_of(v);
+    uint32_t colour = C_BG;
+    bool hit = !q.inside;  /* pixels past the picture's edge have nothing to find */
+    scan_range(fp, 0, len(f), q, hit, colour, lds);
+    if (!hit) colour = uncovered(q.row, q.col);
+    store_tile(v, q, f, colour, lds, out);
+}
+#endif /* __HIPCC__ */
 }  // namespace d2dr
 #endif /* D2D_RASTER_H */

@@ -3,10 +3,11 @@
 // Three kernels over the shared code of d2d_raster.h:
 //   setup_kernel    one lane per (frame, list slot): the frame's primitive list, fp64 -> fp32, into the
 //                   ctx workspace (the per-frame work: trigonometry, path samples, nearest obstacle)
-//   raster_kernel   one workgroup per 64 x 4 pixel tile: culls the list against the tile 256 primitives
-//                   at a time (ballot + compact into LDS, top of the list first), every pixel scans the
-//                   survivors and stops at its first hit; the tile's RGB bytes are staged in LDS and
-//                   leave as dwords (bytes only at a row's unaligned ends)
+//   raster_kernel   one workgroup per 64 x 4 pixel tile (d2d_raster.h's tile walk, shared with
+//                   libd2d_hud.so): culls the list against the tile 256 primitives at a time (ballot +
+//                   compact into LDS, top of the list first), every pixel scans the survivors and stops
+//                   at its first hit; the tile's RGB bytes are staged in LDS and leave as dwords (bytes
+//                   only at a row's unaligned ends)
 //   scatter_kernel  the plot: one lane per path segment, atomicMax(id[pixel], path + 1); the raster
 //                   kernel's plot form resolves id -> rgb between the background and the colour bar
 // No render call allocates or synchronises; all launches are ordered on the caller's stream.
@@ -34,8 +35,6 @@ int32_t fail(int32_t code, const char* fmt, ...) {
     g_err = buf;
     return code;
 }
-
-constexpr int TW = 64, TH = 4, NT = TW * TH;  // tile = one wave per pixel row
 
 struct FrameArgs {
     const d2d_scn* scn;
@@ -66,99 +65,35 @@ __global__ __launch_bounds__(NT) void setup_kernel(Prim* __restrict__ prims, int
     prims[(size_t)f * (size_t)cap + (size_t)slot] = build_prim(in, v, slot);
 }
 
-// Primitives [lo, hi) of the list, top first, 256 at a time: cull against the tile, compact the
-// survivors into LDS in list order, then every unresolved pixel scans them.
-__device__ __forceinline__ void scan_range(const Prim* __restrict__ fp, int32_t lo, int32_t hi, int32_t tx0, int32_t tc1,
-                                           int32_t ty0, int32_t tr1, int32_t row, int32_t col, float x, float y,
-                                           bool& hit, uint32_t& colour, Prim* s_prim, int32_t* s_wcnt) {
-    const int32_t t = (int32_t)threadIdx.x, lane = t & 63, w = t >> 6;
-    for (int32_t base = hi; base > lo; base -= NT) {
-        if (!__syncthreads_or(hit ? 0 : 1)) break;  // every pixel of the tile has its colour (uniform)
-        const int32_t idx = base - 1 - t;
-        // the primitive as three 16-byte words (a.xyzw, b.xy = p[0..5]; b.z = rgbk; b.w, c.xyz = c0, c1, r0, r1)
-        const uint4* src = reinterpret_cast<const uint4*>(fp + (idx >= lo ? idx : lo));
-        const uint4 qa = src[0], qb = src[1], qc = src[2];
-        const bool keep = idx >= lo && (qb.z >> 24) != K_NONE && (int32_t)qb.w <= tc1 && (int32_t)qc.x >= tx0 &&
-                          (int32_t)qc.y <= tr1 && (int32_t)qc.z >= ty0;
-        const unsigned long long b = __ballot(keep);
-        if (lane == 0) s_wcnt[w] = __popcll(b);
-        __syncthreads();
-        int32_t off = 0, total = 0;
-#pragma unroll
-        for (int k = 0; k < NT / 64; ++k) {
-            const int32_t c = s_wcnt[k];
-            off += (k < w) ? c : 0;
-            total += c;
-        }
-        if (keep) {
-            uint4* dst = reinterpret_cast<uint4*>(s_prim + off + __popcll(b & ((1ull << lane) - 1ull)));
-            dst[0] = qa, dst[1] = qb, dst[2] = qc;
-        }
-        __syncthreads();
-        if (!hit)
-            for (int32_t k = 0; k < total; ++k)
-                if (covers(s_prim[k], row, col, x, y)) {
-                    colour = s_prim[k].rgbk;
-                    hit = true;
-                    break;
-                }
-    }
-}
-
+// One tile of one frame (d2d_raster.h has the walk).  A frame's picture is its list over the background;
+// the plot's is the colour bar, then the path ids, then the background list.
 __global__ __launch_bounds__(NT) void raster_kernel(const Prim* __restrict__ prims, int32_t cap, View v,
                                                     const int32_t* __restrict__ trail_len, int32_t max_trail,
                                                     const uint32_t* __restrict__ ids, const uint8_t* __restrict__ rgb,
                                                     uint8_t* __restrict__ out) {
-    __shared__ Prim s_prim[NT];
-    __shared__ int32_t s_wcnt[NT / 64];
-    __shared__ uint8_t s_rgb[TH][TW * 3];
-    const int32_t t = (int32_t)threadIdx.x, lane = t & 63, w = t >> 6;
-    const int32_t tiles_x = (v.W + TW - 1) / TW;
-    const int32_t tx0 = ((int32_t)blockIdx.x % tiles_x) * TW, ty0 = ((int32_t)blockIdx.x / tiles_x) * TH;
+    __shared__ TileLds lds;
     const int32_t f = (int32_t)blockIdx.y;
-    const int32_t col = tx0 + lane, row = ty0 + w;
-    const int32_t tc1 = (tx0 + TW - 1 < v.W - 1) ? tx0 + TW - 1 : v.W - 1;  // the tile's last column / row inside
-    const int32_t tr1 = (ty0 + TH - 1 < v.H - 1) ? ty0 + TH - 1 : v.H - 1;
-    const bool inside = col <= tc1 && row <= tr1;
     const Prim* fp = prims + (size_t)f * (size_t)cap;
-    const int32_t np = list_len(v, trail_len, max_trail, f);
-    const float x = pixel_x(v, col), y = pixel_y(v, row);
+    if (!v.plot) {
+        walk_tile(
+            fp, v, f, [&](int32_t fr) { return list_len(v, trail_len, max_trail, fr); },
+            [](int32_t, int32_t) { return C_BG; }, lds, out);
+        return;
+    }
+    const Tile q = tile_of(v);
     uint32_t colour = C_BG;
-    bool hit = !inside;  // pixels past the picture's edge have nothing to find
-    if (v.plot) {
-        scan_range(fp, N_FIXED, np, tx0, tc1, ty0, tr1, row, col, x, y, hit, colour, s_prim, s_wcnt);  // colour bar
-        if (!hit) {
-            const uint32_t id = ids[(size_t)row * (size_t)v.W + (size_t)col];
-            if (id > 0u) {
-                const uint8_t* q = rgb + 3 * (size_t)(id - 1u);
-                colour = D2DR_RGB(q[0], q[1], q[2]);
-                hit = true;
-            }
+    bool hit = !q.inside;  // pixels past the picture's edge have nothing to find
+    scan_range(fp, N_FIXED, list_len(v, trail_len, max_trail, f), q, hit, colour, lds);  // colour bar
+    if (!hit) {
+        const uint32_t id = ids[(size_t)q.row * (size_t)v.W + (size_t)q.col];
+        if (id > 0u) {
+            const uint8_t* c = rgb + 3 * (size_t)(id - 1u);
+            colour = D2DR_RGB(c[0], c[1], c[2]);
+            hit = true;
         }
-        scan_range(fp, 0, N_FIXED, tx0, tc1, ty0, tr1, row, col, x, y, hit, colour, s_prim, s_wcnt);
-    } else {
-        scan_range(fp, 0, np, tx0, tc1, ty0, tr1, row, col, x, y, hit, colour, s_prim, s_wcnt);
     }
-    if (inside) {
-        s_rgb[w][3 * lane] = (uint8_t)(colour & 255u);
-        s_rgb[w][3 * lane + 1] = (uint8_t)((colour >> 8) & 255u);
-        s_rgb[w][3 * lane + 2] = (uint8_t)((colour >> 16) & 255u);
-    }
-    __syncthreads();
-    if (row > tr1) return;
-    // wave w stores pixel row `row`: bytes up to the first 4-byte boundary, dwords, bytes after the last
-    const int32_t nbytes = 3 * (tc1 - tx0 + 1);
-    uint8_t* g = out + (((size_t)f * (size_t)v.H + (size_t)row) * (size_t)v.W + (size_t)tx0) * 3;
-    int32_t head = (int32_t)((4u - (uint32_t)((uintptr_t)g & 3u)) & 3u);
-    head = head < nbytes ? head : nbytes;
-    const int32_t ndw = (nbytes - head) >> 2, tail0 = head + 4 * ndw;
-    if (lane < head) g[lane] = s_rgb[w][lane];
-    if (lane < ndw) {
-        const uint8_t* s = &s_rgb[w][head + 4 * lane];
-        *reinterpret_cast<uint32_t*>(g + head + 4 * lane) =
-            (uint32_t)s[0] | ((uint32_t)s[1] << 8) | ((uint32_t)s[2] << 16) | ((uint32_t)s[3] << 24);
-    }
-    if (lane < nbytes - tail0) g[tail0 + lane] = s_rgb[w][tail0 + lane];
+    scan_range(fp, 0, N_FIXED, q, hit, colour, lds);
+    store_tile(v, q, f, colour, lds, out);
 }
 
 __global__ __launch_bounds__(NT) void scatter_kernel(View v, const float* __restrict__ xy, const int32_t* __restrict__ len,

@@ -292,10 +292,11 @@ class Drone2dVecEnv:
         return C.c_void_p(t.data_ptr()) if t is not None else None
 
     def close(self):
-        r = getattr(self, "_renderer", None)
-        if r is not None:
-            r.close()
-            self._renderer = None
+        for name in ("_renderer", "_hud_renderer"):
+            r = getattr(self, name, None)
+            if r is not None:
+                r.close()
+                setattr(self, name, None)
         if getattr(self, "_h", None):
             torch.cuda.synchronize(self.device)
             self._lib.d2d_destroy(self._h)
@@ -491,27 +492,29 @@ class Drone2dVecEnv:
         table = self.scenario_table(lo, hi - lo + 1)
         return (abi.D2DScn * len(ids))(*[table[int(k) - lo] for k in slots])
 
-    def render(self, env_ids=None, size=256, layers: int | None = None, trails=None) -> torch.Tensor:
+    def render(self, env_ids=None, size=256, layers: int | None = None, trails=None, text: bool = False,
+               arcs: bool = False, shades=None) -> torch.Tensor:
         """Frames of the envs ``env_ids`` (default: the first min(num_envs, 16)) as they are now:
         uint8 [K, H, W, 3] on the env's device, drawn by libd2d_render.so (drone2d_amd.render has the
         picture model).  ``size``: an int or (H, W); ``layers``: a mask of render.L_* (default all);
         ``trails``: (xy float32 [K, T, 2] world positions, length int32 [K]) or None.  Each frame shows
         the env's running scenario, its state, its current observation's closest and lookahead points
-        and the last action's forces.  The renderer and its library are created on first use."""
+        and the last action's forces.  The renderer and its library are created on first use.
+        ``text``: the six lines of reward terms from the last step's info table; ``arcs``: the angle
+        arcs of the three guide lines; ``shades``: a ``hud.ShadeRecorder`` over the same ``env_ids`` or a
+        (poses float64 [K, S, 3], count int32 [K]) pair.  Any of the three goes through libd2d_hud.so
+        (drone2d_amd.hud); with all at their defaults nothing of it is loaded."""
         from . import render as R
+
+        if text or arcs or shades is not None:
+            return self._render_hud(env_ids, size, layers, trails, bool(text), bool(arcs), shades)
 
         ids = self._render_ids(env_ids)
         k = len(ids)
         h, w = R._size(size)
         if k == 0:
             return torch.empty((0, h, w, 3), dtype=torch.uint8, device=self.device)
-        tr = tl = None
-        if trails is not None:
-            tr, tl = trails
-            tr = torch.as_tensor(tr, dtype=torch.float32)
-            tl = torch.as_tensor(tl, dtype=torch.int32)
-            if tr.dim() != 3 or tuple(tr.shape[::2]) != (k, 2) or tuple(tl.shape) != (k,):
-                raise ValueError("trails must be (xy [K, T, 2], length [K])")
+        tr, tl = self._render_trails(trails, k)
         need_trail = int(tr.shape[1]) if tr is not None else 0
         r = getattr(self, "_renderer", None)
         if r is None or r.max_frames < k or r.max_trail < need_trail:
@@ -519,8 +522,31 @@ class Drone2dVecEnv:
             if r is not None:
                 r.close()
             r = self._renderer = R.Renderer(self.device, max_frames=caps[0], max_trail=caps[1])
-        if tr is not None and tr.shape[1] < r.max_trail:  # the library's trail rows are max_trail long
-            tr = torch.cat([tr, tr.new_zeros(k, r.max_trail - tr.shape[1], 2)], 1)
+        tr = self._pad_rows(tr, r.max_trail)  # the library's trail rows are max_trail long
+        return r.render(*self._render_inputs(r, ids), tr, tl, size=(h, w), screen=(self.cfg.screen_w, self.cfg.screen_h),
+                        layers=R.L_ALL if layers is None else int(layers))
+
+    @staticmethod
+    def _render_trails(trails, k: int):
+        if trails is None:
+            return None, None
+        tr, tl = trails
+        tr = torch.as_tensor(tr, dtype=torch.float32)
+        tl = torch.as_tensor(tl, dtype=torch.int32)
+        if tr.dim() != 3 or tuple(tr.shape[::2]) != (k, 2) or tuple(tl.shape) != (k,):
+            raise ValueError("trails must be (xy [K, T, 2], length [K])")
+        return tr, tl
+
+    @staticmethod
+    def _pad_rows(t, n: int):
+        """[K, m, c] -> [K, n, c], zero-filled (None stays None)."""
+        if t is None or t.shape[1] >= n:
+            return t
+        return torch.cat([t, t.new_zeros(t.shape[0], n - t.shape[1], t.shape[2])], 1)
+
+    def _render_inputs(self, r, ids):
+        """What a frame of each of ``ids`` is drawn from, on the device: the running scenario's record,
+        the state columns, the current observation and the last action (None before the first step)."""
         st, ist = self.get_state()
         dids = ids.to(self.device)
         if not self.cfg.scn_pool:
@@ -530,9 +556,50 @@ class Drone2dVecEnv:
         else:
             scn = r.scn_tensor(self.render_scenarios(ids, ist))
         act = getattr(self, "_last_actions", None)
-        return r.render(scn, st[:, dids], self._bufs[self._k]["obs"][dids], act[dids] if act is not None else None,
-                        tr, tl, size=(h, w), screen=(self.cfg.screen_w, self.cfg.screen_h),
-                        layers=R.L_ALL if layers is None else int(layers))
+        return scn, st[:, dids], self._bufs[self._k]["obs"][dids], act[dids] if act is not None else None
+
+    def _render_hud(self, env_ids, size, layers, trails, text, arcs, shades) -> torch.Tensor:
+        """``render`` with the text overlay, the arcs or the shades: the same inputs, and the info
+        table's rows and the shade lists, through ``hud.HudRenderer``."""
+        from . import hud as H
+        from . import render as R
+
+        if text and not self.with_info:
+            raise ValueError("render(text=True) prints the step's info table: the env needs with_info=True")
+        ids = self._render_ids(env_ids)
+        k = len(ids)
+        h, w = R._size(size)
+        if k == 0:
+            return torch.empty((0, h, w, 3), dtype=torch.uint8, device=self.device)
+        tr, tl = self._render_trails(trails, k)
+        sp = sc = None
+        if shades is not None:
+            if isinstance(shades, H.ShadeRecorder):
+                if not np.array_equal(shades.env_ids, ids.numpy()):
+                    raise ValueError("the ShadeRecorder tracks other env_ids than render was asked for")
+                shades = shades.shades()
+            sp = torch.as_tensor(shades[0], dtype=torch.float64)
+            sc = torch.as_tensor(shades[1], dtype=torch.int32)
+            if sp.dim() != 3 or tuple(sp.shape[::2]) != (k, 3) or sp.shape[1] < 1 or tuple(sc.shape) != (k,):
+                raise ValueError("shades must be a ShadeRecorder or (poses [K, S, 3], count [K])")
+        need_trail = int(tr.shape[1]) if tr is not None else 0
+        need_shades = int(sp.shape[1]) if sp is not None else 0
+        r = getattr(self, "_hud_renderer", None)
+        if r is None or r.max_frames < k or r.max_trail < need_trail or r.max_shades < need_shades:
+            caps = (max(k, 16, r.max_frames if r else 0), max(need_trail, r.max_trail if r else 0),
+                    max(need_shades, r.max_shades if r else 0))
+            if r is not None:
+                r.close()
+            r = self._hud_renderer = H.HudRenderer(self.device, max_frames=caps[0], max_trail=caps[1], max_shades=caps[2])
+        tr = self._pad_rows(tr, r.max_trail)  # the library's rows are max_trail / max_shades long
+        if sp is not None and need_shades < r.max_shades:
+            sp = self._pad_rows(sp, r.max_shades)
+            sc = sc.clamp(max=need_shades)  # a count beyond the caller's capacity must not reach into the padding
+        mask = (R.L_ALL if layers is None else int(layers)) & R.L_ALL
+        mask |= (H.L_TEXT if text else 0) | (H.L_ARCS if arcs else 0) | (H.L_SHADE if sp is not None else 0)
+        info = self._bufs[self._k]["info"][ids.to(self.device)] if text else None
+        return r.render(*self._render_inputs(r, ids), tr, tl, info, (sp, sc) if sp is not None else None, size=(h, w),
+                        screen=(self.cfg.screen_w, self.cfg.screen_h), layers=mask)
 
     def episode_stats(self, clear: bool = True) -> torch.Tensor:
         """float64 [8]: (sum return, episodes, successes, fails, collisions, sum APE, sum len, 0)."""
@@ -587,7 +654,9 @@ class Drone2dEnv:
     (the reference builds float64 from the same expressions); the spawn draw comes from the
     library's Philox stream instead of Python's unseeded ``random``; ``render`` draws
     ``rgb_array`` frames with the project's own picture model (drone2d_amd.render) and opens no
-    window (``render_sim`` / ``render_shade`` / ``render_text`` are ignored).
+    window.  ``render(mode="rgb_array", hud=True)`` adds what ``render_text`` / ``render_shade`` /
+    ``shade_distance`` switch on in the reference, and the angle arcs (drone2d_amd.hud); without
+    ``hud`` those keys are ignored, as ``render_sim`` always is.
     """
 
     metadata = {"render.modes": ["rgb_array"]}
@@ -600,7 +669,12 @@ class Drone2dEnv:
         self.observation_space = self._venv.observation_space
         self.flight_path = []
         self._done = False
+        self._shades = None  # render(hud=True)'s one-env recorder, kept from construction when render_shade is set
         self.reset()  # the reference spawns in __init__ (drone_2d_env.py:144)
+        if self.kwargs.get("render_shade"):
+            from .hud import ShadeRecorder
+
+            self._shades = ShadeRecorder(self._venv, [0], distance=float(self.kwargs.get("shade_distance", 75)))
 
     def seed(self, seed=None):
         if seed is not None:
@@ -611,11 +685,15 @@ class Drone2dEnv:
         obs = self._venv.reset()
         self._done = False
         self.flight_path = []
+        if self._shades is not None:
+            self._shades.restart()
         return obs[0].double().cpu().numpy()
 
     def step(self, action):
         a = torch.as_tensor(np.asarray(action, dtype=np.float32)).reshape(1, 2)
         obs, rew, term, trunc, info = self._venv.step(a)
+        if self._shades is not None:
+            self._shades.update(torch.zeros_like(term), torch.zeros_like(trunc))  # no auto-reset here: never a restart
         o = obs[0].double().cpu().numpy()
         r = float(rew[0].item())
         done = bool(term[0].item() or trunc[0].item()) or self._done  # self.done is sticky (:594)
@@ -629,10 +707,11 @@ class Drone2dEnv:
         self._done = done
         return o, r, done, d
 
-    def render(self, mode="human", close=False):
+    def render(self, mode="human", close=False, hud=False):
         """``mode="rgb_array"``: the frame at the screen size, uint8 [screensize_y, screensize_x, 3],
         with the flight path so far as the trail when ``render_path`` is set.  ``"human"``: None (no
-        window is opened)."""
+        window is opened).  ``hud=True``: the angle arcs, the text overlay when ``render_text`` is set
+        (once a step has filled the info table) and the shades when ``render_shade`` is."""
         if mode != "rgb_array":
             return None
         H, W = int(self.kwargs["screensize_y"]), int(self.kwargs["screensize_x"])
@@ -644,7 +723,11 @@ class Drone2dEnv:
             xy[0, :len(fp), 0] = fp[:, 0]
             xy[0, :len(fp), 1] = float(self.kwargs["screensize_y"]) - fp[:, 1]
             trails = (xy, np.array([len(fp)], np.int32))
-        return self._venv.render([0], size=(H, W), trails=trails)[0].cpu().numpy()
+        if not hud:
+            return self._venv.render([0], size=(H, W), trails=trails)[0].cpu().numpy()
+        text = bool(self.kwargs.get("render_text")) and hasattr(self._venv, "_last_actions")
+        return self._venv.render([0], size=(H, W), trails=trails, text=text, arcs=True,
+                                 shades=self._shades)[0].cpu().numpy()
 
     def close(self):
         self._venv.close()

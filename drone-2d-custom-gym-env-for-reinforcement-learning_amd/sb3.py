@@ -124,11 +124,16 @@ class SB3VecEnv(_Base):
     def close(self):
         self.venv.close()
 
-    def get_images(self, size=256):
+    def get_images(self, size=256, hud=False):
         """The frames of the first min(num_envs, 16) envs (``Drone2dVecEnv.render``), a list of uint8
         [H, W, 3] arrays.  65 536 pictures are nobody's monitor: the cap keeps VecVideoRecorder and
-        ``render`` usable on large batches."""
-        frames = self.venv.render(size=size).cpu().numpy()
+        ``render`` usable on large batches.  ``hud=True`` adds the angle arcs and, once a step has
+        filled the info table, the text overlay (drone2d_amd.hud)."""
+        if hud:
+            text = hasattr(self.venv, "_last_actions")
+            frames = self.venv.render(size=size, text=text, arcs=True).cpu().numpy()
+        else:
+            frames = self.venv.render(size=size).cpu().numpy()
         return [f for f in frames]
 
     def render(self, mode=None):

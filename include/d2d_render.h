@@ -26,7 +26,8 @@
  *      6 velocity line    7 line to the nearest obstacle's centre
  *      8 obstacles        9 frame box, then both motor boxes (the bodies' own poses)
  *      10 force vectors   11 target dot at wp_last     12 trail
- *    Not drawn: the text overlay, the three arcs, the shade sprites, the mouse target.
+ *    Not drawn by this library: the text overlay, the three arcs, the shade sprites (libd2d_hud.so draws
+ *    them around this list: d2d_hud.h), the mouse target.
  *  - Arithmetic: the primitive list of a frame is built in fp64 (d2d_pmath.h's sincos for the body
  *    angles, defined for |angle| <= 8) and rounded once to fp32; the per-pixel tests are fp32 add,
  *    mul, div and compare only.  The CPU twins below run the same functions (csrc/render/
