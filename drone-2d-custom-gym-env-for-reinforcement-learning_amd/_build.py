@@ -38,6 +38,11 @@ HUD_SRC = os.path.join(PKG_DIR, "csrc", "hud", "d2d_hud.hip")
 HUD_HDRS = [os.path.join(PKG_DIR, "csrc", "hud", "d2d_hud_core.h"), os.path.join(PKG_DIR, "csrc", "hud", "d2d_font.h"),
             os.path.join(REPO, "include", "d2d_hud.h"), *RENDER_HDRS]
 HUD_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_hud.so")
+# the GIF encoder (include/d2d_gif.h), a library beside the renderer under csrc/gif/; it takes the colour
+# constants of the renderer's and the HUD's headers and nothing else of them
+GIF_SRC = os.path.join(PKG_DIR, "csrc", "gif", "d2d_gif.hip")
+GIF_HDRS = [os.path.join(PKG_DIR, "csrc", "gif", "d2d_gif_core.h"), os.path.join(REPO, "include", "d2d_gif.h"), *HUD_HDRS]
+GIF_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_gif.so")
 # the fused evaluation step (include/d2d_eval.h), a library of its own under csrc/eval/
 EVAL_SRC = os.path.join(PKG_DIR, "csrc", "eval", "d2d_eval.hip")
 EVAL_HDRS = [os.path.join(PKG_DIR, "csrc", "eval", "d2d_eval_math.h"), os.path.join(REPO, "include", "d2d_eval.h")]
@@ -114,6 +119,15 @@ def build_hud(force: bool = False, verbose: bool = False) -> str:
     return HUD_OUT
 
 
+def build_gif(force: bool = False, verbose: bool = False) -> str:
+    """The GIF encoder (libd2d_gif.so), with the env's flags (integer code: the host twin and the kernels
+    give the same bytes whatever the flags).  Compiled by ``build()`` or by the first use of
+    ``drone2d_amd.gif`` that finds it missing."""
+    if force or needs_build(GIF_OUT, GIF_SRC, GIF_HDRS):
+        _compile(GIF_SRC, GIF_OUT, verbose)
+    return GIF_OUT
+
+
 def build_eval(force: bool = False, verbose: bool = False) -> str:
     """The evaluation step (libd2d_eval.so), with the PPO library's flags (float32 arithmetic, FMAs
     contracted within an expression).  Compiled by ``build()`` or by the first evaluation that finds
@@ -144,7 +158,7 @@ def build_norm(force: bool = False, verbose: bool = False) -> str:
 
 def build(force: bool = False, verbose: bool = False, exact: bool = False) -> str:
     """The in-tree libraries: the env (libdrone2d_hip.so: every mode, one scenario layout), the PPO
-    update kernels (libd2d_ppo.so), the renderer (libd2d_render.so) and its HUD (libd2d_hud.so), the evaluation step
+    update kernels (libd2d_ppo.so), the renderer (libd2d_render.so), its HUD (libd2d_hud.so) and the GIF encoder (libd2d_gif.so), the evaluation step
     (libd2d_eval.so), the episode monitor (libd2d_monitor.so), reward normalisation (libd2d_norm.so)
     and, with ``exact``, the env's exact-trig build."""
     stale = os.path.join(PKG_DIR, "_lib", "libdrone2d_hip_rm.so")  # rounds 1-3's second layout build
@@ -158,6 +172,7 @@ def build(force: bool = False, verbose: bool = False, exact: bool = False) -> st
         _compile(PPO_SRC, PPO_OUT, verbose, PPO_FLAGS)
     build_render(force, verbose)
     build_hud(force, verbose)
+    build_gif(force, verbose)
     build_eval(force, verbose)
     build_monitor(force, verbose)
     build_norm(force, verbose)

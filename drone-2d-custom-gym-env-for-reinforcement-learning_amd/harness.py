@@ -356,6 +356,25 @@ def save_gif(frames, path: str, fps: int = 60) -> None:
     _save(frames, path, fps)
 
 
-__all__ = ["MlpActor", "run_first_episodes", "flight_path_lists", "summary", "write_results",
+def record_gifs(venv, policy, out_dir: str, scenario: str, agent: str, env_ids=(0,), **kw) -> list:
+    """The reference's per-scenario animation (main.py:266-295, ``Gifs/<agent>/<scenario>.gif``), recorded
+    and encoded on the device by ``gif.record_episodes`` (its keyword arguments pass through): the first
+    episode of each of ``env_ids`` of the HIP batch ``venv`` under ``policy``.  One env writes
+    ``<out_dir>/Gifs/<agent>/<scenario>.gif``, several write ``<scenario>_<k>.gif``, k counting ``env_ids``.
+    Needs no Pillow; returns the paths."""
+    from . import gif
+
+    rec = gif.record_episodes(venv, policy, env_ids, **kw)
+    d = os.path.join(out_dir, "Gifs", str(agent))
+    os.makedirs(d, exist_ok=True)
+    names = [f"{scenario}.gif"] if len(rec.gifs) == 1 else [f"{scenario}_{k}.gif" for k in range(len(rec.gifs))]
+    paths = [os.path.join(d, name) for name in names]
+    for p, b in zip(paths, rec.gifs):
+        with open(p, "wb") as f:
+            f.write(b)
+    return paths
+
+
+__all__ = ["MlpActor", "run_first_episodes", "flight_path_lists", "summary", "write_results", "record_gifs",
            "write_results_rank0", "plot_flight_paths", "plot_inputs", "flight_path_colours", "save_gif",
            "selection_table", "write_selection", "SELECTION_COLUMNS"]
