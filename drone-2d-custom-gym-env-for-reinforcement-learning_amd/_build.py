@@ -55,6 +55,11 @@ MONITOR_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_monitor.so")
 NORM_SRC = os.path.join(PKG_DIR, "csrc", "norm", "d2d_norm.hip")
 NORM_HDRS = [os.path.join(REPO, "include", "d2d_norm.h")]
 NORM_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_norm.so")
+# the arena maps (include/d2d_heat.h), a library of its own under csrc/heat/
+HEAT_SRC = os.path.join(PKG_DIR, "csrc", "heat", "d2d_heat.hip")
+HEAT_HDRS = [os.path.join(PKG_DIR, "csrc", "heat", "d2d_heat_core.h"), os.path.join(REPO, "include", "d2d_heat.h"),
+             os.path.join(REPO, "include", "drone2d.h")]
+HEAT_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_heat.so")
 
 # -ffp-contract=off: the kernels follow the reference's NumPy evaluation order (explicit fma() only
 # where NumPy/OpenBLAS fuses); no fast-math: IEEE inf/NaN semantics are part of the contract.
@@ -156,11 +161,20 @@ def build_norm(force: bool = False, verbose: bool = False) -> str:
     return NORM_OUT
 
 
+def build_heat(force: bool = False, verbose: bool = False) -> str:
+    """The arena maps (libd2d_heat.so), with the env's flags (-ffp-contract=off: the cell function's
+    float32 operations round one by one, as the host twin's do; everything else is integer).  Compiled
+    by ``build()`` or by the first ``heatmap.ArenaMaps`` on a HIP device that finds it missing."""
+    if force or needs_build(HEAT_OUT, HEAT_SRC, HEAT_HDRS):
+        _compile(HEAT_SRC, HEAT_OUT, verbose)
+    return HEAT_OUT
+
+
 def build(force: bool = False, verbose: bool = False, exact: bool = False) -> str:
     """The in-tree libraries: the env (libdrone2d_hip.so: every mode, one scenario layout), the PPO
     update kernels (libd2d_ppo.so), the renderer (libd2d_render.so), its HUD (libd2d_hud.so) and the GIF encoder (libd2d_gif.so), the evaluation step
-    (libd2d_eval.so), the episode monitor (libd2d_monitor.so), reward normalisation (libd2d_norm.so)
-    and, with ``exact``, the env's exact-trig build."""
+    (libd2d_eval.so), the episode monitor (libd2d_monitor.so), reward normalisation (libd2d_norm.so),
+    the arena maps (libd2d_heat.so) and, with ``exact``, the env's exact-trig build."""
     stale = os.path.join(PKG_DIR, "_lib", "libdrone2d_hip_rm.so")  # rounds 1-3's second layout build
     if os.path.exists(stale):
         os.remove(stale)
@@ -176,4 +190,5 @@ def build(force: bool = False, verbose: bool = False, exact: bool = False) -> st
     build_eval(force, verbose)
     build_monitor(force, verbose)
     build_norm(force, verbose)
+    build_heat(force, verbose)
     return OUT

@@ -250,10 +250,41 @@ def _records(venv, fin, rows_np, xy_np, nobs) -> dict:
     return out
 
 
+def _check_maps(maps):
+    """``maps`` (None, a grid size or (Gy, Gx)) as None or (Gy, Gx); with more than one rank a ``ValueError``."""
+    if maps is None:
+        return None
+    from . import harness, heatmap
+
+    grid = heatmap.parse_grid(maps)
+    if harness._dist_world()[2] > 1:
+        raise ValueError("maps with more than one rank: summing the shards' planes is not built; evaluate on one rank")
+    return grid
+
+
+def _group_maps(counts: dict, g: int, idx, spawn_obs, fin, rows_np, xy_np) -> dict:
+    """The ``"maps"`` entry of a result dict: group ``g``'s planes [6, Gy, Gx] and ``outside`` [6], the
+    reset positions of its envs ``idx`` and, with a flight buffer, what ``heatmap.from_result`` recomputes
+    the planes from (the recorder's raw buffer, not trimmed: an unfinished env flew all of it)."""
+    out = {"planes": counts["planes"][g], "outside": counts["outside"][g], "spawn_obs": spawn_obs[idx]}
+    if xy_np is not None:
+        # (a group that is the whole batch takes the buffer itself: a fancy index would copy all of it)
+        whole = len(idx) == xy_np.shape[1]
+        out.update(flight_obs=xy_np if whole else xy_np[:, idx], finished=fin[idx], rows=rows_np[idx])
+    return out
+
+
+def _host_maps(grid, raw: dict, env_group, n_groups: int) -> dict:
+    """The planes of a batch flown by ``harness.run_first_episodes`` (``records=False``, with its flight buffer)."""
+    from . import heatmap
+
+    return heatmap.from_flight(raw["spawn_xy"], raw["xy"], raw["finished"], raw["rows"], env_group, n_groups, grid)
+
+
 @torch.no_grad()
 def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0, max_steps: int | None = None,
                     n_obstacles: int | None = None, flight_paths: bool = False, check_every: int = 16,
-                    noise: str = "philox", keep_actions: bool = False, graph: bool = False) -> dict:
+                    noise: str = "philox", keep_actions: bool = False, graph: bool = False, maps=None) -> dict:
     """Step ``venv`` under ``policy`` (an ``ActorCritic``, a ``harness.MlpActor`` or a ``ppo.PPO``)
     until every env has finished its first episode; the result dict of
     ``harness.run_first_episodes`` (+ ``actions`` [steps, n, 2] with ``keep_actions``: this rank's).
@@ -272,8 +303,14 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
     ``graph``: replay the loop as a captured HIP graph (a throw-away ``EvalLoop``): the same result
     dict, bit for bit.  It needs a HIP batch, ``noise="philox"``, ``keep_actions=False`` and one rank.
 
+    ``maps`` (a grid size or (Gy, Gx)): also bin the episodes into arena maps while they fly
+    (``heatmap.ArenaMaps``, one more launch per env step); the result gains ``"maps"``: ``planes`` uint32
+    [6, Gy, Gx], ``outside`` [6], the reset positions ``spawn_obs`` and, with ``flight_paths``, the
+    recorder's raw buffers (``heatmap.from_result`` recomputes the planes from them).  Every other key is
+    what it is without ``maps``.  One rank only.
+
     A batch that is not a HIP ``Drone2dVecEnv`` (the CPU oracle backend of the tests) goes through
-    ``harness.run_first_episodes``."""
+    ``harness.run_first_episodes`` (and its maps through ``heatmap.from_flight`` of the flight buffer)."""
     from . import harness
     from .env import Drone2dVecEnv
 
@@ -281,18 +318,35 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
         raise ValueError("noise must be 'philox' or 'torch'")
     if graph:
         _check_graph(venv, noise, keep_actions)
+    grid = _check_maps(maps)
+    n = int(venv.num_envs)
     if not isinstance(venv, Drone2dVecEnv):
         if keep_actions:
             raise ValueError("keep_actions needs a HIP batch")
-        return harness.run_first_episodes(venv, as_mlp_actor(policy), deterministic=deterministic, seed=seed,
-                                          max_steps=max_steps, n_obstacles=n_obstacles, flight_paths=flight_paths,
-                                          check_every=check_every)
+        kw = dict(deterministic=deterministic, seed=seed, max_steps=max_steps, n_obstacles=n_obstacles,
+                  check_every=check_every)
+        if grid is None:
+            return harness.run_first_episodes(venv, as_mlp_actor(policy), flight_paths=flight_paths, **kw)
+        raw = harness.run_first_episodes(venv, as_mlp_actor(policy), flight_paths=True, records=False, **kw)
+        xy_np = raw["xy"] if flight_paths else None
+        out = _records(venv, raw["finished"], raw["rows"], xy_np, raw["n_obstacles"])
+        out["maps"] = _group_maps(_host_maps(grid, raw, None, 1), 0, np.arange(n), raw["spawn_xy"], raw["finished"],
+                                  raw["rows"], xy_np)
+        return out
+    am = None
+    if grid is not None:
+        from . import heatmap
+
+        am = heatmap.ArenaMaps(venv, grid, cap=max_steps)
     fin, rows_np, xy_np, nobs, actions, _ = _fly(venv, actor_tensors(policy, venv.device), None, deterministic, seed,
                                                  max_steps, n_obstacles, flight_paths, check_every, noise, keep_actions,
-                                                 graph=graph)
+                                                 graph=graph, maps=am)
     out = _records(venv, fin, rows_np, xy_np, nobs)
     if keep_actions:
         out["actions"] = actions
+    if am is not None:
+        out["maps"] = _group_maps(am.counts(), 0, np.arange(n), am.spawn_obs.cpu().numpy(), fin, rows_np, xy_np)
+        am.close()
     return out
 
 
@@ -313,11 +367,12 @@ def _check_graph(venv, noise, keep_actions) -> None:
 
 
 def _fly(venv, ws, bank, deterministic, seed, max_steps, n_obstacles, flight_paths, check_every, noise, keep_actions,
-         extra=(), graph=False):
+         extra=(), graph=False, maps=None):
     """The closed loop of ``evaluate_policy`` on a HIP batch under one actor (``ws``, its seven tensors)
     or a policy bank (``bank``: a ``D2DEvalBank`` whose tensors the caller keeps alive): the recorder's
     arrays over the whole batch in global env order (gathered over the ranks, and with them the
-    per-env arrays in ``extra``), the obstacle count, and this rank's actions [steps, n, 2]."""
+    per-env arrays in ``extra``), the obstacle count, and this rank's actions [steps, n, 2].  ``maps``: a
+    ``heatmap.ArenaMaps`` of this batch, cleared, begun after the reset and stepped after every env step."""
     from . import harness
 
     if not venv.with_info:
@@ -325,7 +380,7 @@ def _fly(venv, ws, bank, deterministic, seed, max_steps, n_obstacles, flight_pat
     if graph:
         _check_graph(venv, noise, keep_actions)
         loop = EvalLoop(venv, None, deterministic=deterministic, flight_paths=flight_paths, check_every=check_every,
-                        graph=True, max_steps=max_steps, n_obstacles=n_obstacles, _actor=(ws, bank))
+                        graph=True, max_steps=max_steps, n_obstacles=n_obstacles, _actor=(ws, bank), _maps=maps)
         return loop.run(seed, extra=extra)
     lib = load()
     dev = venv.device
@@ -344,6 +399,9 @@ def _fly(venv, ws, bank, deterministic, seed, max_steps, n_obstacles, flight_pat
     step = (lambda a, st: _step(lib, a, st)) if bank is None else (lambda a, st: _step_bank(lib, a, bank, st))
     with torch.cuda.device(dev):
         obs = venv.reset(seed=seed)
+        if maps is not None:
+            maps.clear()
+            maps.begin(obs)
         finished = torch.zeros(n, dtype=torch.uint8, device=dev)
         rows = torch.zeros(n, abi.INFO_DIM, dtype=torch.float32, device=dev)
         remaining = torch.full((1,), n, dtype=torch.int32, device=dev)
@@ -377,6 +435,8 @@ def _fly(venv, ws, bank, deterministic, seed, max_steps, n_obstacles, flight_pat
                 break
             # the env's outputs are double-buffered: this step's set stays valid through the next call
             obs, _, term, trunc, info = venv.step(act_env)
+            if maps is not None:
+                maps.step(obs, term, trunc, venv.terminal_obs, info)
             a.prev_term, a.prev_trunc, a.prev_info = term.data_ptr(), trunc.data_ptr(), info.data_ptr()
             a.prev_term_obs = venv.terminal_obs.data_ptr()
             a.finished, a.rows, a.remaining = finished.data_ptr(), rows.data_ptr(), remaining.data_ptr()
@@ -422,11 +482,16 @@ class EvalLoop:
     The segment holds the actor's tensors by address and ``actor_tensors`` makes no copy of float32
     device parameters, so a replay reads the live weights; ``run`` recaptures when one of the seven
     addresses (the bank's one), the seed (the env step takes it by value) or the env's ``generation``
-    is not what the segment was captured with.  ``graph=False``: every run is ``_fly``'s eager loop."""
+    is not what the segment was captured with.  ``graph=False``: every run is ``_fly``'s eager loop.
+
+    ``maps`` (a grid size or (Gy, Gx)): the loop owns a ``heatmap.ArenaMaps`` (``self.maps``; one group,
+    or one per policy of the bank): every ``run`` clears it and begins it eagerly after the reset, and its
+    step call follows every env step, inside the captured segment too; ``self.maps.counts()`` after a
+    run are that run's planes."""
 
     def __init__(self, venv, policy_or_bank, env_policy=None, *, deterministic: bool = False,
                  flight_paths: bool = False, check_every: int = 16, graph: bool = True, max_steps: int | None = None,
-                 n_obstacles: int | None = None, _actor=None):
+                 n_obstacles: int | None = None, maps=None, _actor=None, _maps=None):
         from .env import Drone2dVecEnv
 
         if graph:
@@ -449,6 +514,14 @@ class EvalLoop:
                 self.bank = _as_bank(policy_or_bank).to(venv.device)
                 self._ep = torch.from_numpy(check_env_policy(env_policy, int(venv.num_envs),
                                                              self.bank.n_policies)).to(venv.device)
+        self.maps = _maps  # _fly's ArenaMaps, or the loop's own
+        grid = _check_maps(maps)
+        if grid is not None and _maps is None:
+            from . import heatmap
+
+            groups = self._ep.cpu().numpy() if self._ep is not None else None
+            self.maps = heatmap.ArenaMaps(venv, grid, groups, self.bank.n_policies if self.bank is not None else None,
+                                          cap=max_steps)
         self.K = self.check_every + (self.check_every & 1)
         self.captures = 0       # segments captured so far (1 after any number of runs of unmoved weights)
         self._g = None
@@ -490,7 +563,7 @@ class EvalLoop:
             venv.set_state(*self._snap)
         if not self.graph:
             return _fly(venv, ws, cb, self.deterministic, seed, self.max_steps, self.n_obstacles, self.flight_paths,
-                        self.check_every, "philox", False, extra)
+                        self.check_every, "philox", False, extra, maps=self.maps)
         lib = load()
         dev = venv.device
         n = int(venv.num_envs)
@@ -509,6 +582,10 @@ class EvalLoop:
             self._ws = ws  # (alive while the segment points at them)
             venv._k = self._k0
             obs = venv.reset(seed=seed)
+            hm = self.maps
+            if hm is not None:
+                hm.clear()
+                hm.begin(obs)
             B["finished"].zero_()
             B["rows"].zero_()
             B["remaining"].fill_(n)
@@ -525,6 +602,8 @@ class EvalLoop:
             def env_step():
                 # the env's outputs are double-buffered: this step's set stays valid through the next call
                 o, _, term, trunc, info = venv.step(B["act_env"])
+                if hm is not None:
+                    hm.step(o, term, trunc, venv.terminal_obs, info)
                 a.obs = o.data_ptr()
                 a.prev_term, a.prev_trunc, a.prev_info = term.data_ptr(), trunc.data_ptr(), info.data_ptr()
                 a.prev_term_obs = venv.terminal_obs.data_ptr()
@@ -696,7 +775,8 @@ class BankActor(torch.nn.Module):
 @torch.no_grad()
 def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool = False, seed: int = 0,
                       max_steps: int | None = None, n_obstacles: int | None = None, flight_paths: bool = False,
-                      check_every: int = 16, noise: str = "philox", keep_actions: bool = False, graph: bool = False):
+                      check_every: int = 16, noise: str = "philox", keep_actions: bool = False, graph: bool = False,
+                      maps=None):
     """``evaluate_policy`` for a batch whose envs belong to different agents: env i flies under policy
     ``env_policy[i]`` of ``bank`` (a ``PolicyBank`` or a list of policies), one ``d2d_eval_step_bank``
     per env step.  Returns one result dict per policy (a list), each what ``evaluate_policy`` returns,
@@ -709,7 +789,8 @@ def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool
     env id.  Under ``torch.distributed`` every rank passes its shard's slice of the map (and of
     ``split``); the records are gathered in global env order and split afterwards.  A batch that is not
     a HIP ``Drone2dVecEnv`` goes through ``harness.run_first_episodes`` under a ``BankActor``.
-    ``graph``: as in ``evaluate_policy``."""
+    ``graph``: as in ``evaluate_policy``.  ``maps``: as in ``evaluate_policy``, one group of planes per
+    result: per policy, or per (policy, label) pair with ``split``."""
     from . import harness
     from .env import Drone2dVecEnv
 
@@ -717,6 +798,7 @@ def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool
         raise ValueError("noise must be 'philox' or 'torch'")
     if graph:
         _check_graph(venv, noise, keep_actions)
+    grid = _check_maps(maps)
     bank = _as_bank(bank)
     n = int(venv.num_envs)
     ep = check_env_policy(env_policy, n, bank.n_policies)
@@ -726,33 +808,58 @@ def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool
         if labels.dtype.kind not in "iu" or labels.shape != (n,):
             raise ValueError(f"split must be an integer array of shape [{n}]")
     extra = (ep,) if labels is None else (ep, labels)
-    actions = None
+    # one group of planes per result (with maps there is one rank: the local arrays are the batch's)
+    pairs = sorted(set(zip(ep.tolist(), labels.tolist()))) if labels is not None else None
+    groups = n_groups = None
+    if grid is not None:
+        if pairs is None:
+            groups, n_groups = ep, bank.n_policies
+        else:
+            where = {ps: g for g, ps in enumerate(pairs)}
+            groups = np.array([where[ps] for ps in zip(ep.tolist(), labels.tolist())], np.int32).reshape(n)
+            n_groups = max(len(pairs), 1)
+    actions = counts = spawn_obs = None
     if not isinstance(venv, Drone2dVecEnv):
         if keep_actions:
             raise ValueError("keep_actions needs a HIP batch")
         raw = harness.run_first_episodes(venv, BankActor(bank, ep), deterministic=deterministic, seed=seed,
-                                         max_steps=max_steps, n_obstacles=n_obstacles, flight_paths=flight_paths,
-                                         check_every=check_every, records=False, extra=extra)
-        fin, rows_np, xy_np, nobs, extra = raw["finished"], raw["rows"], raw["xy"], raw["n_obstacles"], raw["extra"]
+                                         max_steps=max_steps, n_obstacles=n_obstacles,
+                                         flight_paths=flight_paths or grid is not None, check_every=check_every,
+                                         records=False, extra=extra)
+        fin, rows_np, nobs, extra = raw["finished"], raw["rows"], raw["n_obstacles"], raw["extra"]
+        xy_np = raw["xy"] if flight_paths else None
+        if grid is not None:
+            counts, spawn_obs = _host_maps(grid, raw, groups, n_groups), raw["spawn_xy"]
     else:
         bank = bank.to(venv.device)
         ep_dev = torch.from_numpy(ep).to(venv.device)
+        am = None
+        if grid is not None:
+            from . import heatmap
+
+            am = heatmap.ArenaMaps(venv, grid, groups, n_groups, cap=max_steps)
         fin, rows_np, xy_np, nobs, actions, extra = _fly(venv, None, bank.c_bank(ep_dev), deterministic, seed, max_steps,
                                                          n_obstacles, flight_paths, check_every, noise, keep_actions,
-                                                         extra, graph=graph)
+                                                         extra, graph=graph, maps=am)
+        if am is not None:
+            counts, spawn_obs = am.counts(), am.spawn_obs.cpu().numpy()
+            am.close()
     g_ep, g_labels = extra[0], (extra[1] if labels is not None else None)
 
-    def subset(mask, local_mask):
+    def subset(mask, local_mask, group):
         idx = np.flatnonzero(mask)
         out = _records(venv, fin[idx], rows_np[idx], xy_np[:, idx] if xy_np is not None else None, nobs)
         if keep_actions:
             out["actions"] = actions[:, np.flatnonzero(local_mask)]
+        if counts is not None:
+            out["maps"] = _group_maps(counts, group, idx, spawn_obs, fin, rows_np, xy_np)
         return out
 
     if labels is None:
-        return [subset(g_ep == p, ep == p) for p in range(bank.n_policies)]
-    pairs = sorted(set(zip(g_ep.tolist(), g_labels.tolist())))
-    return {(p, s): subset((g_ep == p) & (g_labels == s), (ep == p) & (labels == s)) for p, s in pairs}
+        return [subset(g_ep == p, ep == p, p) for p in range(bank.n_policies)]
+    g_pairs = sorted(set(zip(g_ep.tolist(), g_labels.tolist())))
+    return {(p, s): subset((g_ep == p) & (g_labels == s), (ep == p) & (labels == s), g)
+            for g, (p, s) in enumerate(g_pairs)}
 
 
 def sweep_layout(n_policies: int, n_scenarios: int, runs: int) -> tuple:
@@ -767,13 +874,14 @@ def sweep_layout(n_policies: int, n_scenarios: int, runs: int) -> tuple:
 
 
 def sweep(bank, scenarios, runs: int, *, seed: int = 0, deterministic: bool = False, flight_paths: bool = False,
-          env_kwargs: dict | None = None, graph: bool = False) -> dict:
+          env_kwargs: dict | None = None, graph: bool = False, maps=None) -> dict:
     """Every agent of ``bank`` on every scenario, ``runs`` first episodes each, as one batch of
     P S R envs (``sweep_layout``) in one closed loop: {agent name: {scenario name: result dict}}.
     ``scenarios``: names of static scenarios or ``Scenario`` objects (a curriculum stage is refused:
     pass a fresh-curriculum batch to ``evaluate_policies``); ``env_kwargs``: default ``ENV_TEST_CONFIG``.
     Every (agent, scenario, run) is an env of its own global id, so its spawn and noise draws are its own.
-    ``graph``: as in ``evaluate_policy``."""
+    ``graph``: as in ``evaluate_policy``.  ``maps``: as in ``evaluate_policy``, one group of planes per
+    (agent, scenario)."""
     from .config import CURRICULUM_STAGES, ENV_TEST_CONFIG
     from .env import Drone2dVecEnv, is_curriculum
 
@@ -786,12 +894,13 @@ def sweep(bank, scenarios, runs: int, *, seed: int = 0, deterministic: bool = Fa
     if len(set(names)) != len(names):
         raise ValueError("sweep: scenario names must be unique")
     ep, es = sweep_layout(bank.n_policies, len(scenarios), runs)
+    _check_maps(maps)
     if not bank.device.type == "cuda":
         raise ValueError("sweep runs on a HIP device: build the bank there")
     venv = Drone2dVecEnv(len(ep), device=bank.device, seed=seed, with_info=True, env_scenario=es, **kw)
     try:
         res = evaluate_policies(venv, bank, ep, split=es, deterministic=deterministic, seed=seed,
-                                flight_paths=flight_paths, graph=graph)
+                                flight_paths=flight_paths, graph=graph, maps=maps)
     finally:
         venv.close()
     return {bank.names[p]: {names[s]: res[(p, s)] for s in range(len(names))} for p in range(bank.n_policies)}

@@ -127,14 +127,16 @@ def run_first_episodes(venv, policy: MlpActor, *, deterministic: bool = False, s
 
     ``records=False``: instead of the result dict, what it is built from, over the whole (gathered)
     batch in global env order -- ``finished`` bool [n], ``rows`` [n, INFO_DIM], ``xy`` [cap, n, 2] or
-    None, ``n_obstacles``, and ``extra``: the caller's per-env arrays, gathered alike -- for a caller
-    that splits the batch into several result sets (``evaluate.evaluate_policies``)."""
+    None, ``n_obstacles``, ``spawn_xy`` float32 [n, 2] (the reset observation's [6:8]), and ``extra``: the
+    caller's per-env arrays, gathered alike -- for a caller that splits the batch into several result
+    sets (``evaluate.evaluate_policies``) or bins it into arena maps (``heatmap.from_flight``)."""
     dev = venv.device
     pdev = torch.device(policy_device) if policy_device is not None else dev
     dist, rank, world = _dist_world()
     gen = torch.Generator(device=pdev).manual_seed(seed)
     policy = policy.to(pdev)
     obs = venv.reset(seed=seed)
+    spawn_np = obs[:, 6:8].cpu().numpy().copy() if not records else None
     n = venv.num_envs
     offset = int(getattr(venv.cfg, "env_id_base", 0)) if world > 1 else 0
     n_total = n
@@ -168,7 +170,7 @@ def run_first_episodes(venv, policy: MlpActor, *, deterministic: bool = False, s
     extra = tuple(np.asarray(e) for e in extra)
     if world > 1 and gather:
         parts = [None] * world
-        dist.all_gather_object(parts, (offset, fin, rows_np, xy_np, extra))
+        dist.all_gather_object(parts, (offset, fin, rows_np, xy_np, extra, spawn_np))
         parts.sort(key=lambda p: p[0])
         fin = np.concatenate([p[1] for p in parts])
         rows_np = np.concatenate([p[2] for p in parts])
@@ -176,8 +178,11 @@ def run_first_episodes(venv, policy: MlpActor, *, deterministic: bool = False, s
             T = max(p[3].shape[0] for p in parts)
             xy_np = np.concatenate([p[3][:T] for p in parts], 1)
         extra = tuple(np.concatenate([p[4][k] for p in parts]) for k in range(len(extra)))
+        if spawn_np is not None:
+            spawn_np = np.concatenate([p[5] for p in parts])
     if not records:
-        return {"finished": fin, "rows": rows_np, "xy": xy_np, "n_obstacles": nobs, "extra": extra}
+        return {"finished": fin, "rows": rows_np, "xy": xy_np, "n_obstacles": nobs, "extra": extra,
+                "spawn_xy": spawn_np}
     idx = np.flatnonzero(fin)
     recs = [info_dicts(r, nobs) for r in rows_np[idx]]
     out = {
@@ -278,6 +283,40 @@ def plot_flight_paths(m: dict, venv_or_scenario=None, size=None, device=None) ->
         r.close()
 
 
+def plot_background(venv_or_scenario=None, size=None, screen=(1300.0, 1300.0), device=None) -> torch.Tensor:
+    """The picture ``plot_flight_paths`` draws its paths on (the scenario; blank for None or a curriculum
+    stage), without a path: uint8 [H, W, 3] on the device."""
+    from . import render as R
+
+    if size is None:
+        size = (int(screen[1]), int(screen[0]))
+    dev = device if device is not None else getattr(venv_or_scenario, "device", None)
+    if dev is None:
+        dev = torch.device("cuda", torch.cuda.current_device())
+    rec = _plot_scenario(venv_or_scenario, screen)
+    r = R.Renderer(dev, max_frames=1)
+    try:
+        # one path of no points: the renderer draws the scenario and no segment
+        return r.plot_paths(r.scn_tensor([rec]) if rec is not None else None, torch.zeros(1, 1, 2),
+                            torch.zeros(1, dtype=torch.int32), torch.zeros(1, 3, dtype=torch.uint8), size=size,
+                            screen=screen).clone()
+    finally:
+        r.close()
+
+
+def plot_maps(m: dict, venv_or_scenario=None, size=None, device=None, alpha: int = 200, min_count: int = 1) -> dict:
+    """The arena-map pictures of a result that carries ``"maps"``, painted on the device by libd2d_heat.so
+    over ``plot_background``: {"density", "spawn_success", "crashes"} -> uint8 [H, W, 3]
+    (``heatmap.PICTURES``: where the episodes flew, the success rate by spawn cell, where they crashed)."""
+    from . import heatmap
+
+    screen = m.get("screen", (1300.0, 1300.0))
+    bg = plot_background(venv_or_scenario, size, screen, device)
+    planes = np.asarray(m["maps"]["planes"], np.uint32)[None]
+    return {name: heatmap.paint(planes, bg, name, alpha, min_count, device=bg.device)[0].cpu().numpy()
+            for name in heatmap.PICTURES}
+
+
 def summary(m: dict) -> dict:
     """The numbers of the reference's results.txt (main.py:318-325)."""
     runs = m["successes"] + m["fails"]
@@ -291,7 +330,9 @@ def summary(m: dict) -> dict:
 def write_results(m: dict, out_dir: str, scenario: str, agent_nr: str, agent_path: str):
     """The reference's per-scenario files: results.txt + collisions/rewards/apes/time_spent .npy
     (+ the ``flight_paths`` JSON when ``m`` carries them, and then, with a HIP device to draw it on,
-    the overview plot ``plots/<scenario>.png``), main.py:307-389."""
+    the overview plot ``plots/<scenario>.png``), main.py:307-389.  When ``m`` carries arena maps
+    (``evaluate_policy(..., maps=...)``): ``maps.npz`` (``planes``, ``outside``) and, with a HIP device,
+    ``plots/<scenario>_density.png``, ``_spawn_success.png`` and ``_crashes.png`` (``plot_maps``)."""
     os.makedirs(out_dir, exist_ok=True)
     for k in ("collisions", "rewards", "apes", "time_spent"):
         np.save(os.path.join(out_dir, f"{k}.npy"), m[k])
@@ -303,6 +344,14 @@ def write_results(m: dict, out_dir: str, scenario: str, agent_nr: str, agent_pat
 
             os.makedirs(os.path.join(out_dir, "plots"), exist_ok=True)
             write_png(os.path.join(out_dir, "plots", f"{scenario}.png"), plot_flight_paths(m, scenario))
+    if "maps" in m:
+        np.savez(os.path.join(out_dir, "maps.npz"), planes=m["maps"]["planes"], outside=m["maps"]["outside"])
+        if torch.cuda.is_available():
+            from .render import write_png
+
+            os.makedirs(os.path.join(out_dir, "plots"), exist_ok=True)
+            for name, img in plot_maps(m, scenario).items():
+                write_png(os.path.join(out_dir, "plots", f"{scenario}_{name}.png"), img)
     s = summary(m)
     with open(os.path.join(out_dir, f"{scenario}_{agent_nr}_results.txt"), "w") as f:
         for k in ("Successes", "Fails", "Collisions", "Success rate", "Collision rate", "Average APE",
@@ -376,5 +425,5 @@ def record_gifs(venv, policy, out_dir: str, scenario: str, agent: str, env_ids=(
 
 
 __all__ = ["MlpActor", "run_first_episodes", "flight_path_lists", "summary", "write_results", "record_gifs",
-           "write_results_rank0", "plot_flight_paths", "plot_inputs", "flight_path_colours", "save_gif",
+           "write_results_rank0", "plot_flight_paths", "plot_inputs", "plot_background", "plot_maps", "flight_path_colours", "save_gif",
            "selection_table", "write_selection", "SELECTION_COLUMNS"]

@@ -2,7 +2,7 @@
 """Test several saved agents on the test scenarios in one batch (choosing a checkpoint), GPU box.
 
     python tools/sweep_agents.py A.zip B.zip ... | CHECKPOINT_DIR [--scenarios corridor,large] [--envs 1000]
-                                 [--seed 0] [--deterministic] [--flight-paths] [--out DIR]
+                                 [--seed 0] [--deterministic] [--flight-paths] [--maps [GRID]] [--out DIR]
 
 The many-agent companion of tools/test_agent.py, with its options.  The agents are zips (as test_agent.py
 takes them) and / or directories of ``rl_model_<steps>_steps.zip`` checkpoints, each taken in step order.
@@ -54,6 +54,8 @@ def main():
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--deterministic", action="store_true")
     ap.add_argument("--flight-paths", action="store_true")
+    ap.add_argument("--maps", type=int, nargs="?", const=64, default=None, metavar="GRID",
+                    help="bin every (agent, scenario)'s episodes into arena maps of GRID x GRID cells (default 64)")
     ap.add_argument("--out", default=None)
     ap.add_argument("--graph", action="store_true", help="replay the sweep's loop as a captured HIP graph (same results)")
     a = ap.parse_args()
@@ -74,7 +76,7 @@ def main():
     t0 = time.perf_counter()
     bank = evaluate.PolicyBank(paths, names=names, device=torch.device("cuda", 0))
     res = evaluate.sweep(bank, scns, a.envs, seed=a.seed, deterministic=a.deterministic, flight_paths=a.flight_paths,
-                         graph=a.graph)
+                         graph=a.graph, maps=a.maps)
     seconds = round(time.perf_counter() - t0, 3)
     for name, path in zip(names, paths):
         for scn in scns:
