@@ -60,6 +60,10 @@ HEAT_SRC = os.path.join(PKG_DIR, "csrc", "heat", "d2d_heat.hip")
 HEAT_HDRS = [os.path.join(PKG_DIR, "csrc", "heat", "d2d_heat_core.h"), os.path.join(REPO, "include", "d2d_heat.h"),
              os.path.join(REPO, "include", "drone2d.h")]
 HEAT_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_heat.so")
+# disturbed evaluation (include/d2d_disturb.h), a library of its own under csrc/disturb/
+DISTURB_SRC = os.path.join(PKG_DIR, "csrc", "disturb", "d2d_disturb.hip")
+DISTURB_HDRS = [os.path.join(REPO, "include", "d2d_disturb.h")]
+DISTURB_OUT = os.path.join(PKG_DIR, "_lib", "libd2d_disturb.so")
 
 # -ffp-contract=off: the kernels follow the reference's NumPy evaluation order (explicit fma() only
 # where NumPy/OpenBLAS fuses); no fast-math: IEEE inf/NaN semantics are part of the contract.
@@ -170,11 +174,21 @@ def build_heat(force: bool = False, verbose: bool = False) -> str:
     return HEAT_OUT
 
 
+def build_disturb(force: bool = False, verbose: bool = False) -> str:
+    """Disturbed evaluation (libd2d_disturb.so), with the env's flags (-ffp-contract=off: its float32
+    operations round one by one in the order include/d2d_disturb.h states, which the host twin repeats).
+    Compiled by ``build()`` or by the first ``disturb.Disturber`` on a HIP device that finds it missing."""
+    if force or needs_build(DISTURB_OUT, DISTURB_SRC, DISTURB_HDRS):
+        _compile(DISTURB_SRC, DISTURB_OUT, verbose)
+    return DISTURB_OUT
+
+
 def build(force: bool = False, verbose: bool = False, exact: bool = False) -> str:
     """The in-tree libraries: the env (libdrone2d_hip.so: every mode, one scenario layout), the PPO
     update kernels (libd2d_ppo.so), the renderer (libd2d_render.so), its HUD (libd2d_hud.so) and the GIF encoder (libd2d_gif.so), the evaluation step
     (libd2d_eval.so), the episode monitor (libd2d_monitor.so), reward normalisation (libd2d_norm.so),
-    the arena maps (libd2d_heat.so) and, with ``exact``, the env's exact-trig build."""
+    the arena maps (libd2d_heat.so), disturbed evaluation (libd2d_disturb.so) and, with ``exact``, the env's
+    exact-trig build."""
     stale = os.path.join(PKG_DIR, "_lib", "libdrone2d_hip_rm.so")  # rounds 1-3's second layout build
     if os.path.exists(stale):
         os.remove(stale)
@@ -191,4 +205,5 @@ def build(force: bool = False, verbose: bool = False, exact: bool = False) -> st
     build_monitor(force, verbose)
     build_norm(force, verbose)
     build_heat(force, verbose)
+    build_disturb(force, verbose)
     return OUT

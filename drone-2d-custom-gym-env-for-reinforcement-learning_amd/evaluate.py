@@ -284,7 +284,8 @@ def _host_maps(grid, raw: dict, env_group, n_groups: int) -> dict:
 @torch.no_grad()
 def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0, max_steps: int | None = None,
                     n_obstacles: int | None = None, flight_paths: bool = False, check_every: int = 16,
-                    noise: str = "philox", keep_actions: bool = False, graph: bool = False, maps=None) -> dict:
+                    noise: str = "philox", keep_actions: bool = False, graph: bool = False, maps=None,
+                    disturb=None) -> dict:
     """Step ``venv`` under ``policy`` (an ``ActorCritic``, a ``harness.MlpActor`` or a ``ppo.PPO``)
     until every env has finished its first episode; the result dict of
     ``harness.run_first_episodes`` (+ ``actions`` [steps, n, 2] with ``keep_actions``: this rank's).
@@ -309,6 +310,12 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
     recorder's raw buffers (``heatmap.from_result`` recomputes the planes from them).  Every other key is
     what it is without ``maps``.  One rank only.
 
+    ``disturb`` (a ``disturb.Disturbance``, or a ``disturb.Disturber`` built for this batch): fly a
+    disturbed world -- the policy sees ``Disturber.obs`` of the observations and the env gets
+    ``Disturber.act`` of the actions, two more launches per env step, and the one evaluation call becomes a
+    record-only call on the true observations and an act-only call on the disturbed ones.  The recorder,
+    ``flight_paths`` and ``maps`` see the true flight; ``actions`` are the applied ones.  Not with ``graph``.
+
     A batch that is not a HIP ``Drone2dVecEnv`` (the CPU oracle backend of the tests) goes through
     ``harness.run_first_episodes`` (and its maps through ``heatmap.from_flight`` of the flight buffer)."""
     from . import harness
@@ -317,14 +324,20 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
     if noise not in ("philox", "torch"):
         raise ValueError("noise must be 'philox' or 'torch'")
     if graph:
-        _check_graph(venv, noise, keep_actions)
+        _check_graph(venv, noise, keep_actions, disturb)
     grid = _check_maps(maps)
     n = int(venv.num_envs)
+    if disturb is not None:
+        from .disturb import make_disturber
+
+        disturb = make_disturber(disturb, venv, seed)
     if not isinstance(venv, Drone2dVecEnv):
         if keep_actions:
             raise ValueError("keep_actions needs a HIP batch")
         kw = dict(deterministic=deterministic, seed=seed, max_steps=max_steps, n_obstacles=n_obstacles,
                   check_every=check_every)
+        if disturb is not None:
+            kw["disturb"] = disturb
         if grid is None:
             return harness.run_first_episodes(venv, as_mlp_actor(policy), flight_paths=flight_paths, **kw)
         raw = harness.run_first_episodes(venv, as_mlp_actor(policy), flight_paths=True, records=False, **kw)
@@ -340,7 +353,7 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
         am = heatmap.ArenaMaps(venv, grid, cap=max_steps)
     fin, rows_np, xy_np, nobs, actions, _ = _fly(venv, actor_tensors(policy, venv.device), None, deterministic, seed,
                                                  max_steps, n_obstacles, flight_paths, check_every, noise, keep_actions,
-                                                 graph=graph, maps=am)
+                                                 graph=graph, maps=am, disturb=disturb)
     out = _records(venv, fin, rows_np, xy_np, nobs)
     if keep_actions:
         out["actions"] = actions
@@ -350,11 +363,14 @@ def evaluate_policy(venv, policy, *, deterministic: bool = False, seed: int = 0,
     return out
 
 
-def _check_graph(venv, noise, keep_actions) -> None:
+def _check_graph(venv, noise, keep_actions, disturb=None) -> None:
     """What ``graph=True`` cannot do, as a ``ValueError``."""
     from . import harness
     from .env import Drone2dVecEnv
 
+    if disturb is not None:
+        raise ValueError("graph=True with disturb: the replayed loop takes its step index from device memory and the "
+                         "disturbance calls take it by value; fly the disturbed loop eagerly")
     if not isinstance(venv, Drone2dVecEnv):
         raise ValueError("graph=True needs a HIP Drone2dVecEnv: the replayed loop is the device's")
     if noise != "philox":
@@ -367,18 +383,19 @@ def _check_graph(venv, noise, keep_actions) -> None:
 
 
 def _fly(venv, ws, bank, deterministic, seed, max_steps, n_obstacles, flight_paths, check_every, noise, keep_actions,
-         extra=(), graph=False, maps=None):
+         extra=(), graph=False, maps=None, disturb=None):
     """The closed loop of ``evaluate_policy`` on a HIP batch under one actor (``ws``, its seven tensors)
     or a policy bank (``bank``: a ``D2DEvalBank`` whose tensors the caller keeps alive): the recorder's
     arrays over the whole batch in global env order (gathered over the ranks, and with them the
     per-env arrays in ``extra``), the obstacle count, and this rank's actions [steps, n, 2].  ``maps``: a
-    ``heatmap.ArenaMaps`` of this batch, cleared, begun after the reset and stepped after every env step."""
+    ``heatmap.ArenaMaps`` of this batch, cleared, begun after the reset and stepped after every env step.
+    ``disturb``: a ``disturb.Disturber`` of this batch, rewound; the actions are then the applied ones."""
     from . import harness
 
     if not venv.with_info:
         raise ValueError("evaluate_policy needs the env's info rows (with_info=True)")
     if graph:
-        _check_graph(venv, noise, keep_actions)
+        _check_graph(venv, noise, keep_actions, disturb)
         loop = EvalLoop(venv, None, deterministic=deterministic, flight_paths=flight_paths, check_every=check_every,
                         graph=True, max_steps=max_steps, n_obstacles=n_obstacles, _actor=(ws, bank), _maps=maps)
         return loop.run(seed, extra=extra)
@@ -428,7 +445,10 @@ def _fly(venv, ws, bank, deterministic, seed, max_steps, n_obstacles, flight_pat
                 z = torch.randn((n_total, 2), device=dev, dtype=torch.float32, generator=gen)[offset:offset + n]
                 z = z.contiguous()
                 a.noise = z.data_ptr()
-            step(a, stream)
+            if disturb is None:
+                step(a, stream)
+            else:
+                _disturbed_step(step, a, stream, disturb, obs, act_env, t, last)
             if keep_actions and not last:
                 actions.append(act_env.clone())
             if last or (t and t % check_every == 0 and int(remaining.item()) == 0):
@@ -462,6 +482,30 @@ def _fly(venv, ws, bank, deterministic, seed, max_steps, n_obstacles, flight_pat
     return fin, rows_np, xy_np, nobs, actions, extra
 
 
+_RECORD_FIELDS = ("prev_term", "prev_trunc", "prev_info", "prev_term_obs", "finished", "rows", "flight", "remaining")
+
+
+def _disturbed_step(step, a: D2DEvalStepArgs, stream: int, disturb, obs, act_env, t: int, last: bool) -> None:
+    """One policy step of ``_fly`` under a ``disturb.Disturber``, in place of its one evaluation call: the
+    record half alone on the true observations (from step 1 on: ``a`` holds the previous env step's
+    outputs), then -- unless this is the call after the last env step -- the disturbed observations, the act
+    half alone on them, and the disturbance of the actions it wrote.  ``a`` comes back as it was given."""
+    if t >= 1:
+        a.act = 0
+        step(a, stream)
+    if last:
+        return
+    record = [getattr(a, k) for k in _RECORD_FIELDS]
+    for k in _RECORD_FIELDS:
+        setattr(a, k, None)
+    a.act, a.obs = 1, disturb.obs(obs, t).data_ptr()
+    step(a, stream)
+    disturb.act(act_env, t)
+    a.obs = obs.data_ptr()
+    for k, v in zip(_RECORD_FIELDS, record):
+        setattr(a, k, v)
+
+
 class EvalLoop:
     """The closed loop of ``evaluate_policy`` / ``evaluate_policies`` kept for many evaluations of one
     batch: it owns the recorder's buffers, the device call index ``t_dev`` of ``d2d_eval_step_seq`` and,
@@ -487,17 +531,26 @@ class EvalLoop:
     ``maps`` (a grid size or (Gy, Gx)): the loop owns a ``heatmap.ArenaMaps`` (``self.maps``; one group,
     or one per policy of the bank): every ``run`` clears it and begins it eagerly after the reset, and its
     step call follows every env step, inside the captured segment too; ``self.maps.counts()`` after a
-    run are that run's planes."""
+    run are that run's planes.
+
+    ``disturb`` (``graph=False`` only): as in ``evaluate_policy``; a ``Disturbance`` becomes a ``Disturber`` the
+    loop keeps (``self.disturb``), keyed anew by every run's seed."""
 
     def __init__(self, venv, policy_or_bank, env_policy=None, *, deterministic: bool = False,
                  flight_paths: bool = False, check_every: int = 16, graph: bool = True, max_steps: int | None = None,
-                 n_obstacles: int | None = None, maps=None, _actor=None, _maps=None):
+                 n_obstacles: int | None = None, maps=None, disturb=None, _actor=None, _maps=None):
         from .env import Drone2dVecEnv
 
         if graph:
-            _check_graph(venv, "philox", False)
+            _check_graph(venv, "philox", False, disturb)
         elif not isinstance(venv, Drone2dVecEnv):
             raise ValueError("EvalLoop needs a HIP Drone2dVecEnv")
+        self.disturb = self._own_disturb = None
+        if disturb is not None:
+            from .disturb import Disturbance, make_disturber
+
+            self.disturb = make_disturber(disturb, venv, 0)
+            self._own_disturb = isinstance(disturb, Disturbance)  # then its key follows run's seed
         if not venv.with_info:
             raise ValueError("evaluate_policy needs the env's info rows (with_info=True)")
         if int(check_every) < 1:
@@ -562,8 +615,12 @@ class EvalLoop:
         else:
             venv.set_state(*self._snap)
         if not self.graph:
+            if self.disturb is not None:
+                self.disturb.reset()
+                if self._own_disturb:
+                    self.disturb.seed = int(seed) & (2 ** 64 - 1)
             return _fly(venv, ws, cb, self.deterministic, seed, self.max_steps, self.n_obstacles, self.flight_paths,
-                        self.check_every, "philox", False, extra, maps=self.maps)
+                        self.check_every, "philox", False, extra, maps=self.maps, disturb=self.disturb)
         lib = load()
         dev = venv.device
         n = int(venv.num_envs)
@@ -776,7 +833,7 @@ class BankActor(torch.nn.Module):
 def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool = False, seed: int = 0,
                       max_steps: int | None = None, n_obstacles: int | None = None, flight_paths: bool = False,
                       check_every: int = 16, noise: str = "philox", keep_actions: bool = False, graph: bool = False,
-                      maps=None):
+                      maps=None, disturb=None):
     """``evaluate_policy`` for a batch whose envs belong to different agents: env i flies under policy
     ``env_policy[i]`` of ``bank`` (a ``PolicyBank`` or a list of policies), one ``d2d_eval_step_bank``
     per env step.  Returns one result dict per policy (a list), each what ``evaluate_policy`` returns,
@@ -790,17 +847,23 @@ def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool
     ``split``); the records are gathered in global env order and split afterwards.  A batch that is not
     a HIP ``Drone2dVecEnv`` goes through ``harness.run_first_episodes`` under a ``BankActor``.
     ``graph``: as in ``evaluate_policy``.  ``maps``: as in ``evaluate_policy``, one group of planes per
-    result: per policy, or per (policy, label) pair with ``split``."""
+    result: per policy, or per (policy, label) pair with ``split``.  ``disturb``: as in ``evaluate_policy``; a
+    ``Disturber`` built for the batch carries the env -> level map (``sweep`` builds one)."""
     from . import harness
     from .env import Drone2dVecEnv
 
     if noise not in ("philox", "torch"):
         raise ValueError("noise must be 'philox' or 'torch'")
     if graph:
-        _check_graph(venv, noise, keep_actions)
+        _check_graph(venv, noise, keep_actions, disturb)
     grid = _check_maps(maps)
     bank = _as_bank(bank)
     n = int(venv.num_envs)
+    dkw = {}
+    if disturb is not None:
+        from .disturb import make_disturber
+
+        dkw["disturb"] = make_disturber(disturb, venv, seed)
     ep = check_env_policy(env_policy, n, bank.n_policies)
     labels = None
     if split is not None:
@@ -825,7 +888,7 @@ def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool
         raw = harness.run_first_episodes(venv, BankActor(bank, ep), deterministic=deterministic, seed=seed,
                                          max_steps=max_steps, n_obstacles=n_obstacles,
                                          flight_paths=flight_paths or grid is not None, check_every=check_every,
-                                         records=False, extra=extra)
+                                         records=False, extra=extra, **dkw)
         fin, rows_np, nobs, extra = raw["finished"], raw["rows"], raw["n_obstacles"], raw["extra"]
         xy_np = raw["xy"] if flight_paths else None
         if grid is not None:
@@ -840,7 +903,7 @@ def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool
             am = heatmap.ArenaMaps(venv, grid, groups, n_groups, cap=max_steps)
         fin, rows_np, xy_np, nobs, actions, extra = _fly(venv, None, bank.c_bank(ep_dev), deterministic, seed, max_steps,
                                                          n_obstacles, flight_paths, check_every, noise, keep_actions,
-                                                         extra, graph=graph, maps=am)
+                                                         extra, graph=graph, maps=am, **dkw)
         if am is not None:
             counts, spawn_obs = am.counts(), am.spawn_obs.cpu().numpy()
             am.close()
@@ -862,26 +925,36 @@ def evaluate_policies(venv, bank, env_policy, *, split=None, deterministic: bool
             for g, (p, s) in enumerate(g_pairs)}
 
 
-def sweep_layout(n_policies: int, n_scenarios: int, runs: int) -> tuple:
+def sweep_layout(n_policies: int, n_scenarios: int, runs: int, levels: int = 1) -> tuple:
     """(env_policy, env_scenario), int32 [P S R] each, of a sweep batch: policy-major, then scenario,
     then run.  A policy's envs are contiguous, so at most one 64-env chunk per policy boundary holds
-    two policies."""
-    P, S, R = int(n_policies), int(n_scenarios), int(runs)
-    if P < 1 or S < 1 or R < 1:
-        raise ValueError("sweep_layout needs at least one policy, one scenario and one run")
-    return (np.repeat(np.arange(P, dtype=np.int32), S * R),
-            np.tile(np.repeat(np.arange(S, dtype=np.int32), R), P))
+    two policies.  With ``levels`` = L > 1 (a disturbed sweep) the batch is [P S L R] -- policy, scenario,
+    level, run -- and the tuple gains a third array, env_level."""
+    P, S, R, L = int(n_policies), int(n_scenarios), int(runs), int(levels)
+    if P < 1 or S < 1 or R < 1 or L < 1:
+        raise ValueError("sweep_layout needs at least one policy, one scenario, one level and one run")
+    if L == 1:
+        return (np.repeat(np.arange(P, dtype=np.int32), S * R),
+                np.tile(np.repeat(np.arange(S, dtype=np.int32), R), P))
+    return (np.repeat(np.arange(P, dtype=np.int32), S * L * R),
+            np.tile(np.repeat(np.arange(S, dtype=np.int32), L * R), P),
+            np.tile(np.repeat(np.arange(L, dtype=np.int32), R), P * S))
 
 
 def sweep(bank, scenarios, runs: int, *, seed: int = 0, deterministic: bool = False, flight_paths: bool = False,
-          env_kwargs: dict | None = None, graph: bool = False, maps=None) -> dict:
+          env_kwargs: dict | None = None, graph: bool = False, maps=None, disturb=None) -> dict:
     """Every agent of ``bank`` on every scenario, ``runs`` first episodes each, as one batch of
     P S R envs (``sweep_layout``) in one closed loop: {agent name: {scenario name: result dict}}.
     ``scenarios``: names of static scenarios or ``Scenario`` objects (a curriculum stage is refused:
     pass a fresh-curriculum batch to ``evaluate_policies``); ``env_kwargs``: default ``ENV_TEST_CONFIG``.
     Every (agent, scenario, run) is an env of its own global id, so its spawn and noise draws are its own.
     ``graph``: as in ``evaluate_policy``.  ``maps``: as in ``evaluate_policy``, one group of planes per
-    (agent, scenario)."""
+    (agent, scenario).
+
+    ``disturb`` (a list of ``disturb.Disturbance``): the level axis -- the batch is P S L R envs, agents x
+    scenarios x levels x runs, env i under level ``env_level[i]`` of ``sweep_layout``, still one closed loop,
+    and the result is {agent name: {scenario name: {level name: result dict}}} (``disturb.level_names``).
+    With maps: one group of planes per (agent, scenario, level).  Not with ``graph``."""
     from .config import CURRICULUM_STAGES, ENV_TEST_CONFIG
     from .env import Drone2dVecEnv, is_curriculum
 
@@ -893,6 +966,8 @@ def sweep(bank, scenarios, runs: int, *, seed: int = 0, deterministic: bool = Fa
     names = [s if isinstance(s, str) else s.name for s in scenarios]
     if len(set(names)) != len(names):
         raise ValueError("sweep: scenario names must be unique")
+    if disturb is not None:
+        return _sweep_levels(bank, kw, names, runs, seed, deterministic, flight_paths, graph, maps, disturb)
     ep, es = sweep_layout(bank.n_policies, len(scenarios), runs)
     _check_maps(maps)
     if not bank.device.type == "cuda":
@@ -904,6 +979,32 @@ def sweep(bank, scenarios, runs: int, *, seed: int = 0, deterministic: bool = Fa
     finally:
         venv.close()
     return {bank.names[p]: {names[s]: res[(p, s)] for s in range(len(names))} for p in range(bank.n_policies)}
+
+
+def _sweep_levels(bank, kw, names, runs, seed, deterministic, flight_paths, graph, maps, disturb) -> dict:
+    """``sweep`` with the level axis: the labels the batch is split by are scenario * L + level."""
+    from .disturb import Disturber, _levels, level_names
+    from .env import Drone2dVecEnv
+
+    if graph:
+        _check_graph(None, "philox", False, disturb)  # (refused before a batch is built for it)
+    levels = _levels(disturb)
+    lnames, L = level_names(levels), len(levels)
+    lay = sweep_layout(bank.n_policies, len(names), runs, L)
+    ep, es = lay[:2]
+    el = lay[2] if L > 1 else np.zeros(len(ep), np.int32)
+    _check_maps(maps)
+    if not bank.device.type == "cuda":
+        raise ValueError("sweep runs on a HIP device: build the bank there")
+    venv = Drone2dVecEnv(len(ep), device=bank.device, seed=seed, with_info=True, env_scenario=es, **kw)
+    try:
+        d = Disturber(len(ep), levels, el, device=venv.device, env_id_base=int(venv.cfg.env_id_base), seed=seed)
+        res = evaluate_policies(venv, bank, ep, split=es * L + el, deterministic=deterministic, seed=seed,
+                                flight_paths=flight_paths, maps=maps, disturb=d)
+    finally:
+        venv.close()
+    return {bank.names[p]: {names[s]: {lnames[k]: res[(p, s * L + k)] for k in range(L)} for s in range(len(names))}
+            for p in range(bank.n_policies)}
 
 
 __all__ = ["evaluate_policy", "act", "actor_tensors", "as_mlp_actor", "philox_noise_host", "load", "bind", "EvalError",

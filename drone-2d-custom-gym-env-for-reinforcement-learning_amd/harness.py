@@ -96,7 +96,7 @@ def _dist_world():
 def run_first_episodes(venv, policy: MlpActor, *, deterministic: bool = False, seed: int = 0,
                        max_steps: int | None = None, n_obstacles: int | None = None,
                        flight_paths: bool = False, check_every: int = 16, gather: bool = True,
-                       policy_device=None, records: bool = True, extra=()) -> dict:
+                       policy_device=None, records: bool = True, extra=(), disturb=None) -> dict:
     """Step ``venv`` (with info rows) under ``policy`` until every env has finished its first
     episode; per-episode records as the reference's test loop keeps them (main.py:273-281).
 
@@ -129,7 +129,15 @@ def run_first_episodes(venv, policy: MlpActor, *, deterministic: bool = False, s
     batch in global env order -- ``finished`` bool [n], ``rows`` [n, INFO_DIM], ``xy`` [cap, n, 2] or
     None, ``n_obstacles``, ``spawn_xy`` float32 [n, 2] (the reset observation's [6:8]), and ``extra``: the
     caller's per-env arrays, gathered alike -- for a caller that splits the batch into several result
-    sets (``evaluate.evaluate_policies``) or bins it into arena maps (``heatmap.from_flight``)."""
+    sets (``evaluate.evaluate_policies``) or bins it into arena maps (``heatmap.from_flight``).
+
+    ``disturb`` (a ``disturb.Disturbance``, or a ``disturb.Disturber`` / ``HostDisturber`` built for this
+    batch): the policy sees ``disturb.obs`` of the observations and the env gets ``disturb.act`` of the
+    actions; the records and the flight paths are the true flight's."""
+    if disturb is not None:
+        from .disturb import make_disturber
+
+        disturb = make_disturber(disturb, venv, seed)
     dev = venv.device
     pdev = torch.device(policy_device) if policy_device is not None else dev
     dist, rank, world = _dist_world()
@@ -153,7 +161,11 @@ def run_first_episodes(venv, policy: MlpActor, *, deterministic: bool = False, s
         noise = None
         if not deterministic:
             noise = torch.randn((n_total, 2), device=pdev, dtype=torch.float32, generator=gen)[offset:offset + n]
-        a = policy.act(obs.to(pdev), deterministic=deterministic, noise=noise)
+        if disturb is None:
+            a = policy.act(obs.to(pdev), deterministic=deterministic, noise=noise)
+        else:
+            a = policy.act(disturb.obs(obs, t).to(pdev), deterministic=deterministic, noise=noise)
+            a = disturb.act(a.to(dev).contiguous(), t)
         obs, rew, term, trunc, info = venv.step(a)
         done = term | trunc
         new = done & ~finished
@@ -397,6 +409,48 @@ def write_selection(results: dict, out_dir: str) -> list:
     return rows
 
 
+ROBUSTNESS_COLUMNS = ("agent", "scenario", "level", "obs_sigma", "act_sigma", "sensor_dropout", "motor_gain_left",
+                      "motor_gain_right", "act_delay", "episodes", "success_rate", "collision_rate", "average_ape",
+                      "average_flight_time")
+
+
+def robustness_table(results: dict, levels) -> list:
+    """One row (``ROBUSTNESS_COLUMNS``) per (agent, scenario, level) of ``results`` = {agent: {scenario:
+    {level name: result dict}}} (``evaluate.sweep(..., disturb=levels)``), in its order: the level's
+    parameters and ``summary``'s headline numbers."""
+    from .disturb import level_names
+
+    levels = list(levels)
+    by_name = dict(zip(level_names(levels), levels))
+    rows = []
+    for agent, per_scn in results.items():
+        for scn, per_level in per_scn.items():
+            for name, m in per_level.items():
+                s, d = summary(m), by_name[name].as_dict()
+                rows.append((agent, scn, name, d["obs_sigma"], d["act_sigma"], d["sensor_dropout"], d["motor_gain_left"],
+                             d["motor_gain_right"], d["act_delay"], s["Successes"] + s["Fails"], s["Success rate"],
+                             s["Collision rate"], s["Average APE"], s["Average flight time"]))
+    return rows
+
+
+def write_robustness(out_dir: str, results: dict, levels) -> list:
+    """``robustness_table(results, levels)`` as ``robustness.csv`` (a header line, floats by ``repr``) and
+    ``robustness.json`` (a list of objects; NaN written as null) under ``out_dir``; returns the rows."""
+    import csv
+
+    rows = robustness_table(results, levels)
+    os.makedirs(out_dir, exist_ok=True)
+    with open(os.path.join(out_dir, "robustness.csv"), "w", newline="") as f:
+        w = csv.writer(f)
+        w.writerow(ROBUSTNESS_COLUMNS)
+        for r in rows:
+            w.writerow([repr(float(v)) if isinstance(v, float) else v for v in r])
+    with open(os.path.join(out_dir, "robustness.json"), "w") as f:
+        json.dump([{k: (None if isinstance(v, float) and v != v else v) for k, v in zip(ROBUSTNESS_COLUMNS, r)}
+                   for r in rows], f, indent=1)
+    return rows
+
+
 def save_gif(frames, path: str, fps: int = 60) -> None:
     """Frames [T, H, W, 3] as an animated GIF (the reference's per-scenario GIF, main.py:283-300);
     needs Pillow and raises ImportError without it."""
@@ -426,4 +480,5 @@ def record_gifs(venv, policy, out_dir: str, scenario: str, agent: str, env_ids=(
 
 __all__ = ["MlpActor", "run_first_episodes", "flight_path_lists", "summary", "write_results", "record_gifs",
            "write_results_rank0", "plot_flight_paths", "plot_inputs", "plot_background", "plot_maps", "flight_path_colours", "save_gif",
-           "selection_table", "write_selection", "SELECTION_COLUMNS"]
+           "selection_table", "write_selection", "SELECTION_COLUMNS", "robustness_table", "write_robustness",
+           "ROBUSTNESS_COLUMNS"]
