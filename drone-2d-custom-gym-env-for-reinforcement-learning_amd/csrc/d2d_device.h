@@ -53,6 +53,11 @@ __device__ uint64_t d2d_bst[BST_N];
     } while (0)
 #endif
 
+// Loop markers for tools/loop_slots.py: an empty asm statement whose comment names a loop of the
+// path wave (`begin`: a block on the loop's cycle), a block that is not on its hot path (`cold`) or
+// one it takes only some passes (`opt`).  They emit no instruction.
+#define D2D_LOOP_MARK(what) asm volatile("; D2D_LOOP " what)
+
 namespace d2d {
 
 constexpr double PI = 3.141592653589793;      // np.pi
@@ -471,12 +476,20 @@ __device__ __forceinline__ void brent_init(const S& s, const PathK& K, double px
     B.fnfc = B.fx;
 }
 // scipy's loop condition without maxfun: |xf - xm| > tol2 - (b - a) / 2
-__device__ __forceinline__ bool brent_open(const Brent& B) {
+// (BrTol: xm, tol1, tol2 of a state, which the loop test and the next candidate both need: a loop
+// whose test sits at its end hands them to the step instead of computing them twice)
+struct BrTol {
+    double xm, tol1, tol2;
+};
+__device__ __forceinline__ BrTol brent_tol(const Brent& B) {
     const double xm = 0.5 * (B.a + B.b);
     const double tol1 = BR_SQRT_EPS * fabs(B.xf) + BR_XATOL3;
-    const double tol2 = 2.0 * tol1;
-    return fabs(B.xf - xm) > (tol2 - 0.5 * (B.b - B.a));
+    return BrTol{xm, tol1, 2.0 * tol1};
 }
+__device__ __forceinline__ bool brent_open(const Brent& B, const BrTol& T) {
+    return fabs(B.xf - T.xm) > (T.tol2 - 0.5 * (B.b - B.a));
+}
+__device__ __forceinline__ bool brent_open(const Brent& B) { return brent_open(B, brent_tol(B)); }
 __device__ __forceinline__ bool brent_active(const Brent& B) { return brent_open(B) & (B.num < 500); }
 // One scipy iteration in its two halves: brent_cand = the candidate probe of the next step (it sets
 // B.e and B.rat exactly as scipy's iteration does before the evaluation), brent_update = the decision
@@ -487,21 +500,20 @@ struct BrCand {
     double x;
     int ix;
 };
-template <bool KN, class S>
+template <bool KN, bool FT, class S>
 __device__ __forceinline__ int brent_interval(const S& s, const PathK& K, const Brent& B, double x, double ka,
                                               double* kn);
 // KN: the knot scan reads the lane's knots staged in LDS at kn (global-memory tables, closest_u)
-template <bool KN = false, class S>
-__device__ __forceinline__ BrCand brent_cand(const S& s, const PathK& K, Brent& B, double* kn = nullptr) {
+// FT: brent_interval's fall-through form (the env-ordered full-load kernel's loops, see there)
+template <bool KN = false, bool FT = false, class S>
+__device__ __forceinline__ BrCand brent_cand(const S& s, const PathK& K, Brent& B, double* kn, const BrTol& T) {
     const double a = B.a, b = B.b, xf = B.xf, fx = B.fx, nfc = B.nfc, fulc = B.fulc;
     // the upper knot of a's interval, for the one-compare interval test: re-read from a staged (LDS)
     // table; carried in the state (B.ka, B.kxf, from the records the probes already read) when the
     // table is read per lane from global memory (ScnR), where that load sat on every step's chain.
     // (Prefetching a's whole record before the candidate is known, or xf's, measured no faster.)
     const double ka = S::RM ? B.ka : SREC(s, REC_U1, B.ia);
-    const double xm = 0.5 * (a + b);
-    const double tol1 = BR_SQRT_EPS * fabs(xf) + BR_XATOL3;
-    const double tol2 = 2.0 * tol1;
+    const double xm = T.xm, tol1 = T.tol1, tol2 = T.tol2;
     // parabolic candidate (used only when |e| > tol1 and it is acceptable)
     const double r = (xf - nfc) * (fx - B.ffulc);
     double q = (xf - fulc) * (fx - B.fnfc);
@@ -515,6 +527,7 @@ __device__ __forceinline__ BrCand brent_cand(const S& s, const PathK& K, Brent& 
     // division on every step without this branch measured +2 %, profiles/r05/stash/)
     double rat_p = 0.0;
     if (__ballot(par) != 0ull) {
+        D2D_LOOP_MARK("opt par");
         rat_p = div_normal(p + 0.0, q);
         const double xp = xf + rat_p;
         // tol1 * (np.sign(d) + (d == 0)) for d = xm - xf: a, b and xf are finite (the initial
@@ -535,10 +548,14 @@ __device__ __forceinline__ BrCand brent_cand(const S& s, const PathK& K, Brent& 
     // (rat is never -0: e_g = a - xf or b - xf is +0 at worst, the parabolic step is p + 0.0 over
     // |q| or tol1 times a nonzero sign, so copysign gives the same -mx / +mx)
     const double x = xf + copysign(mx, rat);
-    return BrCand{x, brent_interval<KN>(s, K, B, x, ka, kn)};
+    return BrCand{x, brent_interval<KN, FT>(s, K, B, x, ka, kn)};
+}
+template <bool KN = false, bool FT = false, class S>
+__device__ __forceinline__ BrCand brent_cand(const S& s, const PathK& K, Brent& B, double* kn = nullptr) {
+    return brent_cand<KN, FT>(s, K, B, kn, brent_tol(B));
 }
 // the knot interval of a probe x in [B.a, B.b] (ka = us[B.ia + 1])
-template <bool KN, class S>
+template <bool KN, bool FT, class S>
 __device__ __forceinline__ int brent_interval(const S& s, const PathK& K, const Brent& B, double x, double ka,
                                               double* kn) {
     // knot interval of x: one compare once the bracket spans <= 2 intervals (wave-uniform choice).
@@ -551,27 +568,40 @@ __device__ __forceinline__ int brent_interval(const S& s, const PathK& K, const 
     // xf toward the midpoint, and max(|rat|, tol1) then moves it by less than tol1 more.  The margins
     // (tol1 >= 3.3e-7) dwarf the roundings.
     const bool fast = B.ib <= B.ia + 1;
-    int ix;
-    if (__ballot(!fast) == 0ull) {
-        ix = min(B.ia + ((x <= ka) ? 0 : 1), K.nw - 1);
-    } else {
+    // FT: the one-compare index is computed in any case -- three instructions -- and the scan replaces
+    // it, so the common path falls through one untaken branch instead of taking two.  Only the
+    // env-ordered full-load kernel's loops ask for it: the grouped kernel measured slower with it
+    // (mixed, DESIGN.md "Where each lever stands"), and the others keep the code they were measured with.
+    const auto scan_ix = [&]() -> int {
         // the knot scan re-reads the knots each time (an opaque pointer or offset stops the compiler
         // from keeping all 15 in registers across the loop: the fast path does not need them).  With
         // the table in global memory (ScnR) an opaque offset keeps global loads where the opaque
         // pointer made flat ones (fresh curriculum K1 88.9 -> 85.4 us); for a staged (LDS) table the
         // offset form measured 1.3 % slower at 4 096 envs (profiles/r04/ring/), so the flat loads stay.
+        D2D_LOOP_MARK("cold scan");
         if constexpr (S::RM) {
             int z = 0;
             asm volatile("" : "+v"(z));
             if constexpr (KN) {
-                ix = u_index_kn(kn, K.nw, x, z);
+                return u_index_kn(kn, K.nw, x, z);
             } else {
-                ix = u_index_at(s, x, z);
+                return u_index_at(s, x, z);
             }
         } else {
             const S* sp = &s;
             asm volatile("" : "+v"(sp));
-            ix = u_index(*sp, x);
+            return u_index(*sp, x);
+        }
+    };
+    int ix;
+    if constexpr (FT) {
+        ix = min(B.ia + ((x <= ka) ? 0 : 1), K.nw - 1);
+        if (__builtin_expect(__ballot(!fast) != 0ull, 0)) ix = scan_ix();
+    } else {
+        if (__ballot(!fast) == 0ull) {
+            ix = min(B.ia + ((x <= ka) ? 0 : 1), K.nw - 1);
+        } else {
+            ix = scan_ix();
         }
     }
     return ix;
@@ -616,15 +646,15 @@ __device__ __forceinline__ bool brent_update(Brent& B, const BrCand& c, double f
                              // distances are NaN only all together, for a NaN point)
     return le;
 }
-template <bool KN = false, class S>
+template <bool KN = false, bool FT = false, class S>
 __device__ __forceinline__ void brent_step(const S& s, const PathK& K, double px, double py, Brent& B,
-                                           double* kn = nullptr BST_ARG) {
+                                           double* kn = nullptr BST_ARG, const BrTol* tol = nullptr) {
 #ifdef D2D_BSTAMP
     uint64_t bst_t[5];
 #endif
     BST(0, B.xf);
     const bool fast = B.ib <= B.ia + 1;
-    const BrCand c = brent_cand<KN>(s, K, B, kn);
+    const BrCand c = tol ? brent_cand<KN, FT>(s, K, B, kn, *tol) : brent_cand<KN, FT>(s, K, B, kn);
     BST(1, c.x);
     BST(2, c.ix);
     // (a per-lane LDS cache of the probe's interval record for global-memory tables measured slower:
@@ -646,6 +676,16 @@ __device__ __forceinline__ void brent_step(const S& s, const PathK& K, double px
     (void)fast;
 #endif
 }
+// the step of a state whose xm / tol1 / tol2 the caller's loop test has computed already (T)
+template <bool FT = false, class S>
+__device__ __forceinline__ void brent_step_tol(const S& s, const PathK& K, double px, double py, Brent& B,
+                                               const BrTol& T) {
+#ifdef D2D_BSTAMP
+    brent_step<false, FT>(s, K, px, py, B, nullptr, nullptr, &T);
+#else
+    brent_step<false, FT>(s, K, px, py, B, nullptr, &T);
+#endif
+}
 // scipy's `while` loop (maxfun = 500 included).  A lane takes one step per pass of the wave's loop
 // until it is inactive (a finished search stays finished), so at pass `it` an active lane's num is
 // its entry num + it; entry nums are at most BT_K + 1 (a golden-march snapshot), so num < 500 holds
@@ -653,7 +693,7 @@ __device__ __forceinline__ void brent_step(const S& s, const PathK& K, double px
 // (never reached by a search over a finite bracket: the golden steps alone shrink it below xtol in
 // ~60 passes).  brent_step does not advance num; B.num stays the entry count.  (IT_FREE: a caller
 // whose entry nums are larger passes 500 - their bound, bt_finish_join.)
-template <bool KN = false, class S>
+template <bool KN = false, bool FT = false, class S>
 __device__ __forceinline__ void brent_run(const S& s, const PathK& K, double px, double py, Brent& B,
                                           double* kn = nullptr, const int IT_FREE = 500 - (BT_K_MAX + 1)) {
     for (int it = 0;; ++it) {
@@ -663,12 +703,13 @@ __device__ __forceinline__ void brent_run(const S& s, const PathK& K, double px,
             act = act & (B.num + it < 500);
         }
         if (!act) break;
+        D2D_LOOP_MARK("begin run");
 #ifdef D2D_BSTAMP
         uint64_t* bst = nullptr;
         if ((threadIdx.x >> 6) == 2 && blockIdx.x < 1024 && it < 64) bst = d2d_bst + ((size_t)blockIdx.x * 64 + it) * 8;
-        brent_step<KN>(s, K, px, py, B, kn, bst);
+        brent_step<KN, FT>(s, K, px, py, B, kn, bst);
 #else
-        brent_step<KN>(s, K, px, py, B, kn);
+        brent_step<KN, FT>(s, K, px, py, B, kn);
 #endif
     }
 }
@@ -882,6 +923,7 @@ __device__ __forceinline__ void bt_verify(const BtHot* hot, BtLane& L, int k0, i
     int dev = L.dev;
     const int kind = L.kind;
     for (int k = k0; __ballot(k < min(dev, k1)) != 0ull; k += 3) {
+        D2D_LOOP_MARK("begin march");
         // tables in global memory (a lane's own scenario): a lane that is done loads nothing, so a
         // wave's long marches do not drag every lane's table lines in from HBM
         BtIt ha{}, hb{}, hc{};

@@ -385,19 +385,46 @@ __device__ __forceinline__ double bt_finish_join(const SC& s, const BrTab& T, co
             B.fnfc = L.fb;
             B.fx = L.fc;
         }
-        // the loop: as below while an early lane is open and the flag was not seen, and in any case for
-        // its first BT_RIDE passes when the wave has a rider (`go` is wave-uniform)
+        // the loop: while an early lane is open and the flag was not seen, and in any case for its first
+        // BT_RIDE passes when the wave has a rider.  Its control is scalar: a lane steps in a pass exactly
+        // when it is open and the wave goes on, and what the wave goes on is wave-uniform, so the loop
+        // tests the open lanes' mask once per pass instead of a per-lane exit.  A closed lane stays
+        // closed (its state no longer changes), so it may sit in the loop switched off; `it` counts each
+        // lane's own passes.  The masks come from the ballot builtin, which reads the compare's own mask.
         const bool in = early | rider;
+        const uint64_t m_early = __builtin_amdgcn_ballot_w64(early);
+        const uint64_t m_in = __builtin_amdgcn_ballot_w64(in);
+        int ride_end = any_rider ? BT_RIDE : 0;
+        asm volatile("" : "+s"(ride_end));  // (kept a number in a scalar register: one compare per pass)
         uint32_t up = 0u;
         int it = 0;
-        for (;; ++it) {
-            const bool open = in & brent_open(B);
-            const bool go = (any_rider & (it < BT_RIDE)) |
-                            ((__builtin_amdgcn_readfirstlane(up) == 0u) & (__ballot(early & open) != 0ull));
-            if (!(open & (it < IT_JOIN) & go)) break;
-            up = *(const volatile LdsU32*)&fv;
-            brent_step(s, K, px, py, B);
-        }
+        // The two phases are two copies of the loop, so that neither tests what only the other needs:
+        // the riders' passes [0, ride_end) go on while any lane is open and do not look at the flag; the
+        // passes after them, up to the cap, go on while an early lane is open and the flag was not seen.
+        // (A wave whose lanes all close during the riders' passes takes no pass of the second loop, whose
+        // test finds no early lane open either: so where the second loop takes a pass, the first took
+        // all of its own, and the second counts from ride_end.)
+        // The loop test hands the state's xm / tol1 / tol2 to the step.
+        const auto phase = [&](const uint64_t m_sel, const int first, const int lim, const bool flag) {
+            for (int pass = first; pass < lim; ++pass) {
+                const BrTol tol = brent_tol(B);
+                const bool opn = brent_open(B, tol);
+                if (flag && __builtin_amdgcn_readfirstlane(up) != 0u) break;
+                if ((__builtin_amdgcn_ballot_w64(opn) & m_sel) == 0ull) break;
+                if (flag) {
+                    D2D_LOOP_MARK("begin join");
+                } else {
+                    D2D_LOOP_MARK("begin ride");
+                }
+                up = *(const volatile LdsU32*)&fv;
+                if (in & opn) {
+                    brent_step_tol<true>(s, K, px, py, B, tol);
+                    ++it;
+                }
+            }
+        };
+        phase(m_in, 0, ride_end, false);
+        phase(m_early, ride_end, IT_JOIN, true);
         B.num += it;
         flag_wait(fv);
         // the join.  dv: the other wave's first differing step in [BT_EARLY + BT_RIDE, len) for a lane
@@ -431,7 +458,7 @@ __device__ __forceinline__ double bt_finish_join(const SC& s, const BrTab& T, co
             }
         }
         if (__ballot(brent_active(B)) != 0ull)
-            brent_run(s, K, px, py, B, nullptr, 500 - (BT_K_MAX + 1) - IT_JOIN);
+            brent_run<false, true>(s, K, px, py, B, nullptr, 500 - (BT_K_MAX + 1) - IT_JOIN);
         iu = B.ixf;
         return B.xf;
     }
